@@ -16,6 +16,11 @@ Default workload = BASELINE.json configs[2] / configs[3] (SURVEY 8d configs 3 an
 scaling; the checksums of the N slices must add up to the single-GPU checksums (shard-count invariance,
 tests/smoke/test_graph.py:67-127 at full size).  `--scaling weak` gives every GPU its own genome set instead.
 Rank 0 prints ONE JSON line.
+
+A plain run sets up, warms up, times the --steps steps and prints the line (figures derived from those steps' own timings
+included).  `--full` adds what takes work of its own: the checksums of the result and their comparison with the committed
+full-size values, and -- at N = 1, unless --no-cpu-baseline -- the CPU (reference) baseline, the element-wise parity on its
+sample and the end-to-end legs.  `--dump-outputs DIR` writes the last timed step's arrays as .npy files (dump_outputs).
 """
 from __future__ import annotations
 
@@ -360,6 +365,38 @@ def cpu_baseline_and_parity(batch, k, w, n_genomes_sample, is_targets):
     return base, parity, e2e
 
 
+DUMP_SEED = 20261016
+DUMP_ROWS = {"kmers": 1 << 19, "nodes": 1 << 18, "edges": 1 << 18}   # at most ~42 MB of float64 files in all
+HASH_FIELDS = ("hash", "first", "second")                            # full 64-bit values: stored as two exact 32-bit halves
+
+
+def dump_outputs(ix, directory, suffix="", share=1):
+    """What the timed path hands a caller -- Index.export()'s kmers / nodes / edges of the last step -- as float64 .npy files
+    in `directory`, one per field: <array>_<field>.npy, a 64-bit hash as <array>_<field>_hi.npy / _lo.npy (every other field
+    is exact in float64: u32, indices, counts, the f64 penalty).  An array longer than DUMP_ROWS / share is sampled at
+    positions drawn with a fixed seed (the same positions for the same length), written as <array>_index.npy; counts.npy
+    holds the full lengths.  At N > 1 every rank writes its own slice (suffix "_rank<r>", share = N)."""
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    arrays = dict(zip(("kmers", "nodes", "edges"), ix.export()))
+    files = {"counts": np.array([len(a) for a in arrays.values()], np.float64)}
+    for name, a in arrays.items():
+        rows = DUMP_ROWS[name] // share
+        if len(a) > rows:
+            idx = np.sort(np.random.default_rng(DUMP_SEED).choice(len(a), rows, replace=False))
+            a = a[idx]
+            files[f"{name}_index"] = idx.astype(np.float64)
+        for field in a.dtype.names:
+            v = a[field]
+            if field in HASH_FIELDS:
+                files[f"{name}_{field}_hi"] = (v >> np.uint64(32)).astype(np.float64)
+                files[f"{name}_{field}_lo"] = (v & np.uint64(0xFFFFFFFF)).astype(np.float64)
+            else:
+                files[f"{name}_{field}"] = v.astype(np.float64)
+    for name, v in files.items():
+        np.save(os.path.join(directory, f"{name}{suffix}.npy"), v)
+
+
 def golden_checksums(workload, k, w):
     """(entry, "reference" | "self"): the reference-derived full-size values where they exist, else the HIP path's own."""
     from seqwin_amd.device import CHECKSUM_SCHEME
@@ -464,9 +501,17 @@ def main() -> None:
     ap.add_argument("-w", "--windowsize", type=int, default=200)
     ap.add_argument("--cpu-sample-genomes", type=int, default=2048,
                     help="genomes of the workload the CPU reference and the end-to-end leg run on (10 Gbp: ~25 s at 8 threads)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--write-golden", action="store_true", help="record this run's N=1 checksums in tests/golden/")
+    ap.add_argument("--full", action="store_true",
+                    help="also compute the result's checksums and parity, and (N = 1) the CPU baseline and end-to-end legs")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline and end-to-end legs")
+    ap.add_argument("--write-golden", action="store_true", help="with --full: record this run's N=1 checksums in tests/golden/")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's kmers / nodes / edges to DIR as float64 .npy files (see dump_outputs)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.write_golden and not args.full:
+        ap.error("--write-golden needs --full (the checksums are computed there)")
 
     # stdout carries exactly ONE line, the JSON: whatever a library prints there (RCCL's version banner when a communicator is
     # made, for one) goes to stderr -- file descriptor 1 is pointed at stderr for the run, the line is written to the real one
@@ -585,6 +630,9 @@ def main() -> None:
         t = torch.tensor([dt], dtype=torch.float64, device=red_dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
+    if args.dump_outputs:
+        dump_outputs(ix.merged if hasattr(ix, "merged") else ix, args.dump_outputs,
+                     suffix=f"_rank{rank}" if world > 1 else "", share=world)
 
     # per-phase device time of the LAST step's sharded build, max over ranks (stream events: no synchronisation inside the step)
     dist_info = None
@@ -609,7 +657,7 @@ def main() -> None:
         dist.all_reduce(counts)
     n_occ_local = tm.get("n_occ_local", nk)
     # checksums of the whole (concatenated) result: at N > 1 the slices' shares add up modulo 2^64
-    sums = ix.global_checksums() if use_dist else ix.checksums()
+    sums = (ix.global_checksums() if use_dist else ix.checksums()) if args.full else None
 
     if rank == 0:
         ms_per_step = dt / args.steps * 1e3
@@ -677,8 +725,9 @@ def main() -> None:
             "first_build_ms": round(first_build_ms, 3) if first_build_ms is not None else None,
             "counts": {"kmers": tot[0], "nodes": tot[1], "edges": tot[2]},
             "tiles": {key: int(tm.get(key, 0)) for key in ("n_tiles", "tiles_b256", "tiles_b64", "tiles_generic", "tiles_gap", "ovf_tiles")},
-            "checksums": [f"{s:016x}" for s in sums],
         }
+        if sums is not None:
+            out["checksums"] = [f"{s:016x}" for s in sums]
         try:   # how the radix passes rank on this device (the LDS-atomic form needs the device's self-check to pass)
             import ctypes
 
@@ -717,7 +766,8 @@ def main() -> None:
                                                "so this instruction mix cannot reach that peak"}
         parity = {}
         # (one rank holds the whole workload whatever the scaling mode is called; with more ranks only "strong" keeps the genomes)
-        gold, gold_src = golden_checksums(args.workload, k, w) if (scaling == "strong" or world == 1) and not args.genomes else (None, None)
+        gold, gold_src = golden_checksums(args.workload, k, w) if args.full and (scaling == "strong" or world == 1) and not args.genomes \
+            else (None, None)
         if args.write_golden and world == 1 and not use_dist:
             # (only the file of the HIP path's own results; the reference-derived file is written by scripts/pin_fullsize_ref.py alone)
             allg = json.loads(GOLDEN.read_text()) if GOLDEN.exists() else {}
@@ -733,7 +783,7 @@ def main() -> None:
             parity["full_size_vs"] = gold_src
             if gold_src == "reference":
                 parity["full_size_reference"] = {kk: gold[kk] for kk in ("genomes", "reference", "command") if kk in gold}
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             out["cpu_baseline"], ref_par, out["e2e"] = cpu_baseline_and_parity(batch, k, w, args.cpu_sample_genomes, my_targets)
             parity.update(ref_par)
         if parity:

@@ -49,7 +49,8 @@ def build_oracle_lib(force: bool = False) -> Path:
 
 def build_ref(reference_root: str = "/root/reference") -> Path | None:
     """Compile the real reference into oracle/_ref/ when its sources are present."""
-    if not Path(reference_root, "cpp", "src", "seqwin", "build.cpp").exists():
+    # (os.access, not Path.exists: for a user who may not enter the directory, exists() raises instead of answering False)
+    if not os.access(os.path.join(reference_root, "cpp", "src", "seqwin", "build.cpp"), os.R_OK):
         return None
     subprocess.check_call(["make", "-C", str(_HERE), "ref", f"REF={reference_root}"],
                           stdout=subprocess.DEVNULL)

@@ -1,6 +1,6 @@
 # final.sh <tag>: the end-of-round set on the final library -- ragged / salmonella lines, the profile set of the default bench, the GPU suite
 export TMPDIR=/tmp; R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/$1; mkdir -p $O; cd $R
-for wl in ragged500 salmonella500; do timeout -k 10 200 python3 bench.py --workload $wl --no-cpu-baseline > $O/bench_$wl.json 2> $O/bench_$wl.err || exit 1; done
+for wl in ragged500 salmonella500; do timeout -k 10 200 python3 bench.py --workload $wl --full --no-cpu-baseline > $O/bench_$wl.json 2> $O/bench_$wl.err || exit 1; done
 python3 -c "
 import json
 for n in ('ragged500','salmonella500'):

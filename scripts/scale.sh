@@ -15,10 +15,10 @@ for N in 1 2 4 8; do
   [ "$N" -le "$MAXN" ] && [ "$N" -le "$NDEV" ] || continue
   PORT=$((29600 + N))
   if [ "$N" -eq 1 ]; then
-    python3 bench.py --gpus 1 --steps 10 --warmup 2 --no-cpu-baseline > "$OUT/rccl_n$N.json" 2> "$OUT/rccl_n$N.err"
+    python3 bench.py --gpus 1 --steps 10 --warmup 2 --full --no-cpu-baseline > "$OUT/rccl_n$N.json" 2> "$OUT/rccl_n$N.err"
   else
     python3 -m torch.distributed.run --nnodes=1 --nproc-per-node "$N" --master-addr 127.0.0.1 --master-port "$PORT" \
-      bench.py --gpus "$N" --steps 10 --warmup 2 > "$OUT/rccl_n$N.json" 2> "$OUT/rccl_n$N.err"
+      bench.py --gpus "$N" --steps 10 --warmup 2 --full > "$OUT/rccl_n$N.json" 2> "$OUT/rccl_n$N.err"
   fi
   echo "rccl N=$N rc=$?" | tee -a "$OUT/scale.log"
   python3 - "$OUT/rccl_n$N.json" <<'PY' | tee -a "$OUT/scale.log"

@@ -463,7 +463,7 @@ def test_bench_strong_scaling_reproduces_n1_checksums(workload, extra):
     import sys
     from pathlib import Path
     root = Path(__file__).resolve().parent.parent
-    base = [str(root / "bench.py"), "--workload", workload, "--steps", "2", "--warmup", "1", "--no-cpu-baseline"] + extra
+    base = [str(root / "bench.py"), "--workload", workload, "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline"] + extra
 
     def run(cmd, env=None):
         out = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=env)

@@ -346,7 +346,7 @@ def _bench_line(extra_args, env_extra):
     if "torch" in sys.modules:
         sys.modules["torch"].cuda.empty_cache()
     env = dict(os.environ, **env_extra)
-    out = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--no-cpu-baseline"] + extra_args, capture_output=True, text=True,
+    out = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--full", "--no-cpu-baseline"] + extra_args, capture_output=True, text=True,
                          timeout=900, env=env)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]

@@ -652,13 +652,13 @@ def test_native_log_line_reaches_the_root_logger(smoke_paths, caplog):
 
 def test_bench_line_contract():
     """bench.py prints ONE JSON line with the fields the driver reads (metric, value, unit, n_gpus, steps, warmup,
-    ms_per_step, higher_is_better, scaling, vs_baseline, dtype, data, config.workload) plus roofline and -- at N = 1 --
-    cpu_baseline.  Run on the small workload, with a 4-genome CPU sample."""
+    ms_per_step, higher_is_better, scaling, vs_baseline, dtype, data, config.workload) plus roofline and -- with --full at
+    N = 1 -- cpu_baseline.  Run on the small workload, with a 4-genome CPU sample."""
     import json
     import subprocess
     import sys
     root = Path(__file__).resolve().parent.parent
-    out = subprocess.run([sys.executable, str(root / "bench.py"), "--workload", "tiny", "--steps", "2", "--warmup", "1",
+    out = subprocess.run([sys.executable, str(root / "bench.py"), "--workload", "tiny", "--steps", "2", "--warmup", "1", "--full",
                           "--cpu-sample-genomes", "4"], capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
@@ -685,6 +685,35 @@ def test_bench_line_contract():
     assert "traffic" in r
     c = d["cpu_baseline"]
     assert c["kind"] in ("reference", "port") and c["unit"] == "Gbp/s" and c["cores"] >= 1 and c["value"] > 0 and c["sample"]
+
+
+def test_bench_plain_run_dumps_what_the_timed_path_computed(tmp_path):
+    """A plain bench.py run times --steps steps and nothing else (no checksums, parity or CPU baseline: those are --full's);
+    --dump-outputs writes the last step's arrays, which must be what Batch.build_index gives on the same seeded workload."""
+    import json
+    import subprocess
+    import sys
+
+    from bench import SEED, WORKLOADS, dump_outputs   # (the repository root is on sys.path: tests/conftest.py)
+    root = Path(__file__).resolve().parent.parent
+    out = subprocess.run([sys.executable, str(root / "bench.py"), "--workload", "tiny", "--steps", "3", "--warmup", "1",
+                          "--dump-outputs", str(tmp_path / "got")], capture_output=True, text=True, timeout=600)
+    assert out.returncode == 0, out.stderr[-2000:]
+    d = json.loads(out.stdout)
+    assert d["steps"] == 3 and d["ms_per_step"] > 0 and d["value"] > 0 and d["higher_is_better"] is True and d["dtype"] == "u64"
+    assert not {"cpu_baseline", "e2e", "parity", "checksums"} & set(d)
+    G, rpg, rl, anc, snp, _ = WORKLOADS["tiny"]
+    batch = Batch.synthetic(G, rpg, rl, n_ancestors=anc, snp_ppm=snp, seed=SEED)
+    ix = batch.build_index(21, 200, np.arange(G) % 2 == 0)
+    dump_outputs(ix, tmp_path / "exp")
+    ix.close()
+    batch.close()
+    names = sorted(p.name for p in (tmp_path / "exp").iterdir())
+    assert names == sorted(p.name for p in (tmp_path / "got").iterdir()) and "nodes_penalty.npy" in names
+    for n in names:
+        got, exp = np.load(tmp_path / "got" / n), np.load(tmp_path / "exp" / n)
+        assert got.dtype == np.float64 and np.array_equal(got, exp), n
+    assert np.load(tmp_path / "got" / "counts.npy").tolist() == [d["counts"]["kmers"], d["counts"]["nodes"], d["counts"]["edges"]]
 
 
 def test_two_host_threads_two_streams_share_the_block_pool():
