@@ -278,6 +278,41 @@ int sw_index_filter_graph(const sw_index *ix, uint64_t edge_weight_th, sw_index 
 int sw_index_filter_kmers(const sw_index *ix, const sw_index *nodes_from, const uint64_t *used_hashes, uint64_t n_used,
                           sw_index **out);
 
+/* ---- kmers._get_subgraphs (src/seqwin/kmers.py:176-312) on the device (csrc/subgraph.hip) ---------------------------------
+ * Greedy seed expansion of low-penalty subgraphs over a filtered index (sw_index_filter_graph, or sw_index_from_arrays).
+ * Seeds are the nodes of the graph (endpoints of an edge) with penalty <= penalty_th in ascending hash order (kmers.py:237-246);
+ * rng.shuffle depends on the list's length only, so the caller shuffles list(range(n_seeds)) and passes it as seed_perm
+ * (shuffled seed i = seed seed_perm[i]).  The result is the reference's `subgraphs` in commit order (before its final
+ * rng.shuffle, kmers.py:309, which the caller does the same way) and `used`.  Arithmetic in double, as the reference does it. */
+typedef struct sw_subgraphs sw_subgraphs; /* opaque device-resident result of sw_index_subgraphs */
+/* A filtered graph given as host arrays (what _filter_edges_and_nodes returns, kmers.py:132-173), uploaded as an index without
+ * kmers: nodes strictly ascending by hash with finite non-negative penalties (SW_ERR_VALUE otherwise). */
+int sw_index_from_arrays(const sw_node *nodes, uint64_t n_nodes, const sw_edge *edges, uint64_t n_edges, sw_index **out);
+/* Number of seeds at penalty_th (kmers.py:243-245). */
+int sw_index_subgraph_seeds(const sw_index *f, double penalty_th, uint64_t *n_seeds);
+/* The walk (kmers.py:248-301).  max_nodes = UINT64_MAX for None.  seed_perm[n_seeds]: host array, a permutation of
+ * 0 .. n_seeds - 1 (SW_ERR_VALUE otherwise, or if n_seeds is not the number of seeds).  Zero subgraphs is a result here; the
+ * reference's RuntimeError (kmers.py:300-307) is raised by the caller. */
+int sw_index_subgraphs(const sw_index *f, double penalty_th, uint64_t min_nodes, uint64_t max_nodes, const uint64_t *seed_perm,
+                       uint64_t n_seeds, sw_subgraphs **out);
+/* Sizes: subgraphs, their nodes (= |used|), induced edges, nodes of the filtered graph. */
+int sw_subgraphs_sizes(const sw_subgraphs *sg, uint64_t *n_subgraphs, uint64_t *n_sg_nodes, uint64_t *n_induced_edges,
+                       uint64_t *n_nodes);
+/* D2H copies (any pointer may be NULL): offsets[n_subgraphs + 1] and hashes[n_sg_nodes] (ascending inside each subgraph), in
+ * commit order; edge_offsets[n_subgraphs + 1] and edges[n_induced_edges]: the filtered edges with both endpoints in the same
+ * subgraph (nx_graph.subgraph(sg), markers.py:418), grouped by subgraph, in edge order inside a group; used_mask[n_nodes] over
+ * the filtered nodes; used_hashes[n_sg_nodes] ascending. */
+int sw_subgraphs_export(const sw_subgraphs *sg, uint64_t *offsets, uint64_t *hashes, uint64_t *edge_offsets, sw_edge *edges,
+                        uint8_t *used_mask, uint64_t *used_hashes);
+/* counters[10] = { seeds, rounds, expansions run, expansions invalidated (re-run in a later round), seeds skipped as used,
+ * kept expansions, discarded expansions (< min_nodes), largest frontier, spilled expansions, last window size };
+ * ms[3] = { adjacency + seeds, walk, results } (HIP events). */
+int sw_subgraphs_stats(const sw_subgraphs *sg, uint64_t *counters, double *ms);
+void sw_subgraphs_free(sw_subgraphs *sg);
+/* sw_index_filter_kmers with the subgraphs' used nodes (the device `used`, no host set): seqwin::filter_kmers
+ * (filter.cpp:139-201) as kmers.py:113-116 calls it after the walk. */
+int sw_index_filter_kmers_sg(const sw_index *ix, const sw_index *nodes_from, const sw_subgraphs *sg, sw_index **out);
+
 /* ---- multi-GPU merge (one process per GPU; the exchange itself is done by the host side with
  *      torch.distributed / RCCL on the device buffers below).  Together these replace
  *      merge_thread_graphs (cpp/src/seqwin/build_internals.cpp:295-392) across GPUs. -------------- */

@@ -162,11 +162,56 @@ class Index:
         return Index(h)
 
     def filter_kmers(self, nodes_from: "Index", used_hashes) -> "Index":
-        """filter_kmers on device: nodes of ``nodes_from`` whose hash is in ``used_hashes`` + their kmers from self."""
-        used = np.fromiter((int(x) for x in used_hashes), dtype=np.uint64)
+        """filter_kmers on device: nodes of ``nodes_from`` whose hash is in ``used_hashes`` + their kmers from self.
+        ``used_hashes`` may be a :class:`Subgraphs`: its device-resident ``used`` is taken then, with no host set."""
         h = c_vp()
+        if isinstance(used_hashes, Subgraphs):
+            check(lib.sw_index_filter_kmers_sg(self._h, nodes_from._h, used_hashes._h, ctypes.byref(h)))
+            return Index(h)
+        used = np.fromiter((int(x) for x in used_hashes), dtype=np.uint64)
         check(lib.sw_index_filter_kmers(self._h, nodes_from._h, _ptr(used), c_u64(len(used)), ctypes.byref(h)))
         return Index(h)
+
+    @classmethod
+    def from_arrays(cls, nodes, edges) -> "Index":
+        """Upload a filtered graph given as host arrays (what kmers._filter_edges_and_nodes returns): nodes strictly ascending by
+        hash, edges whose endpoints are among them.  An index without kmers, for :meth:`subgraphs`."""
+        nodes = np.ascontiguousarray(nodes, NODE_DTYPE)
+        edges = np.ascontiguousarray(edges, EDGE_DTYPE)
+        h = c_vp()
+        check(lib.sw_index_from_arrays(_ptr(nodes), c_u64(len(nodes)), _ptr(edges), c_u64(len(edges)), ctypes.byref(h)))
+        return cls(h)
+
+    def subgraph_seeds(self, penalty_th: float) -> int:
+        """Number of seeds of the subgraph walk: nodes of the graph with penalty <= penalty_th (kmers.py:243-245)."""
+        n = c_u64()
+        check(lib.sw_index_subgraph_seeds(self._h, ctypes.c_double(float(penalty_th)), ctypes.byref(n)))
+        return n.value
+
+    def subgraphs(self, penalty_th: float, min_nodes: int, max_nodes, rng) -> "Subgraphs":
+        """kmers._get_subgraphs (src/seqwin/kmers.py:176-312) on a filtered index (:meth:`filter_graph`), on the device.
+
+        ``rng`` (random.Random) is used exactly as the reference uses it -- one shuffle of the seeds, one of the subgraphs --
+        and left in the same state: both shuffles are done on index lists of the same lengths.  Raises the reference's
+        RuntimeError when no subgraph is kept."""
+        th = float(penalty_th)
+        n_seeds = self.subgraph_seeds(th)
+        perm = list(range(n_seeds))
+        rng.shuffle(perm)
+        perm = np.asarray(perm, np.uint64)
+        mx = _U64_MAX if max_nodes is None else max(int(max_nodes), 0)
+        h = c_vp()
+        check(lib.sw_index_subgraphs(self._h, ctypes.c_double(th), c_u64(max(int(min_nodes), 0)), c_u64(mx), _ptr(perm),
+                                     c_u64(n_seeds), ctypes.byref(h)))
+        sg = Subgraphs(h)
+        n_sg = sg.sizes()[0]
+        if n_sg == 0:
+            sg.close()
+            raise RuntimeError(NO_SUBGRAPH_MSG)
+        order = list(range(n_sg))
+        rng.shuffle(order)
+        sg.order = np.asarray(order, np.int64)
+        return sg
 
     def save_npz(self, path, record_offsets) -> None:
         """Write ``graph.npz`` exactly as ``--save-graph`` does (src/seqwin/core.py:134-145)."""
@@ -199,6 +244,102 @@ class Index:
             self.close()
         except Exception:
             pass
+
+
+_U64_MAX = (1 << 64) - 1
+NO_SUBGRAPH_MSG = ('No low-penalty subgraph was found. '
+                   'Try decrease --stringency, or increase --penalty-th (penalty threshold, check log for the calculated value)')
+
+
+class Subgraphs:
+    """Low-penalty subgraphs of a filtered index, resident on the device (:meth:`Index.subgraphs`).
+
+    The device keeps them in commit order; ``order`` is the reference's final rng.shuffle of that list (kmers.py:309):
+    subgraph i of the result is committed subgraph order[i]."""
+
+    def __init__(self, handle: c_vp):
+        self._h = handle
+        self.order = np.zeros(0, np.int64)
+
+    def sizes(self):
+        """(subgraphs, their nodes, induced edges, nodes of the filtered graph)"""
+        v = [c_u64() for _ in range(4)]
+        check(lib.sw_subgraphs_sizes(self._h, *[ctypes.byref(x) for x in v]))
+        return tuple(x.value for x in v)
+
+    def csr(self):
+        """(offsets[n_sg + 1], hashes) in the final order, hashes ascending inside every subgraph."""
+        n_sg, n_out, _, _ = self.sizes()
+        offs = np.empty(n_sg + 1, np.uint64)
+        hashes = np.empty(n_out, np.uint64)
+        check(lib.sw_subgraphs_export(self._h, _ptr(offs), _ptr(hashes), None, None, None, None))
+        return _reorder(offs, hashes, self.order)
+
+    def as_reference(self):
+        """(tuple[frozenset[np.uint64], ...], frozenset[np.uint64]): what kmers._get_subgraphs returns."""
+        offs, hashes = self.csr()
+        vals = list(hashes)   # np.uint64 elements, as the reference's sets hold them
+        o = offs.tolist()
+        sgs = tuple(frozenset(vals[o[i]:o[i + 1]]) for i in range(len(o) - 1))
+        return sgs, frozenset(vals)
+
+    def used_hashes(self) -> np.ndarray:
+        """The hashes of all subgraph nodes, ascending."""
+        n_out = self.sizes()[1]
+        out = np.empty(n_out, np.uint64)
+        check(lib.sw_subgraphs_export(self._h, None, None, None, None, None, _ptr(out)))
+        return out
+
+    def used_mask(self) -> np.ndarray:
+        """bool[n] over the filtered graph's nodes."""
+        n = self.sizes()[3]
+        out = np.empty(n, np.uint8)
+        check(lib.sw_subgraphs_export(self._h, None, None, None, None, _ptr(out), None))
+        return out.astype(bool)
+
+    def induced_edges(self):
+        """For every subgraph (final order): the filtered edges with both endpoints in it (nx_graph.subgraph(sg), markers.py:418),
+        in edge order."""
+        n_sg, _, n_ie, _ = self.sizes()
+        offs = np.empty(n_sg + 1, np.uint64)
+        edges = np.empty(n_ie, EDGE_DTYPE)
+        check(lib.sw_subgraphs_export(self._h, None, None, _ptr(offs), _ptr(edges), None, None))
+        o = offs.astype(np.int64)
+        return [edges[o[i]:o[i + 1]] for i in self.order.tolist()]
+
+    def stats(self) -> dict:
+        c = (c_u64 * 10)()
+        ms = (ctypes.c_double * 3)()
+        check(lib.sw_subgraphs_stats(self._h, c, ms))
+        names = ("seeds", "rounds", "expansions", "invalidated", "skipped_used", "kept", "discarded", "max_frontier", "spilled",
+                 "window")
+        d = dict(zip(names, (int(x) for x in c)))
+        d.update(adjacency_ms=ms[0], walk_ms=ms[1], results_ms=ms[2])
+        return d
+
+    def close(self) -> None:
+        if self._h:
+            lib.sw_subgraphs_free(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _reorder(offs: np.ndarray, hashes: np.ndarray, order: np.ndarray):
+    """CSR (offs, hashes) with its rows taken in ``order``."""
+    o = offs.astype(np.int64)
+    lens = np.diff(o)[order]
+    new_offs = np.zeros(len(order) + 1, np.uint64)
+    np.cumsum(lens, out=new_offs[1:])
+    if len(hashes) == 0:
+        return new_offs, hashes
+    starts = o[:-1][order]
+    idx = np.repeat(starts - np.concatenate([[0], np.cumsum(lens)[:-1]]), lens) + np.arange(int(lens.sum()))
+    return new_offs, hashes[idx]
 
 
 _G = np.uint64(0x9E3779B97F4A7C15)
