@@ -260,3 +260,240 @@ def test_release_library_walk():
     r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, cwd=str(ROOT), env=env, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     assert "release ok 8" in r.stdout, r.stdout
+
+
+# ---- adversarial shapes (tests/tools/sg_shapes.py) against goldens recorded from the reference ---------------------------------
+import sg_shapes as S  # noqa: E402
+
+SHAPES = S.load_golden(GOLDEN)
+SG_HOOKS = ("SEQWIN_AMD_SG_WINDOW", "SEQWIN_AMD_SG_LDS_CAP")
+
+
+def _hooks(monkeypatch, **env):
+    for k in SG_HOOKS:
+        monkeypatch.delenv(k, raising=False)
+    for k, v in env.items():
+        monkeypatch.setenv(f"SEQWIN_AMD_SG_{k}", str(v))
+
+
+def _run_shape(ix, case):
+    """(Subgraphs or the error text, rng.random() afterwards) of Index.subgraphs."""
+    rng = random.Random(case["seed"])
+    try:
+        sg = ix.subgraphs(case["penalty_th"], case["min_nodes"], case["max_nodes"], rng)
+    except RuntimeError as e:
+        return str(e), rng.random()
+    return sg, rng.random()
+
+
+def _digest(sg):
+    return S.csr_digest(*sg.csr())
+
+
+def _induced_grouped_ok(sg, nodes, edges):
+    """Subgraphs.induced_edges() == H.induced_edges, computed in one pass (a stable sort by subgraph) for walks with many subgraphs."""
+    offs, hashes = sg.csr()
+    h = np.asarray(nodes["hash"], np.uint64)
+    sg_of = np.full(len(h), -1, np.int64)
+    sg_of[np.searchsorted(h, hashes)] = np.repeat(np.arange(len(offs) - 1), np.diff(offs.astype(np.int64)))
+    a = sg_of[np.searchsorted(h, edges["first"])]
+    b = sg_of[np.searchsorted(h, edges["second"])]
+    hit = np.flatnonzero((a >= 0) & (a == b))
+    hit = hit[np.argsort(a[hit], kind="stable")]
+    got = sg.induced_edges()
+    assert len(got) == len(offs) - 1
+    assert np.array_equal(np.array([len(x) for x in got], np.int64), np.bincount(a[hit], minlength=len(offs) - 1))
+    assert np.array_equal(np.concatenate(got) if got else edges[:0], edges[hit])
+
+
+def _shape_paths(g, case, st):
+    """The kernel paths each family is built to reach."""
+    fam, p = g["family"], g["params"]
+    assert st["kept"] + st["discarded"] + st["skipped_used"] == st["seeds"], st
+    assert st["kept"] == case["n_subgraphs"], st
+    if fam == "star":
+        nf = p["deg"] + max(p.get("deg2", 0) - 1, 0)   # the first accepted leaf leaves the frontier before its neighbours enter
+        if nf <= 1024:
+            assert st["max_frontier"] == nf and st["spilled"] == 0, st
+        else:
+            assert st["spilled"] >= 1, st
+    if fam == "many_seeds":
+        assert st["window"] == 4096 and st["invalidated"] == 0, st
+    if fam == "dense":
+        assert st["invalidated"] > 0, st
+    if fam == "multi_spill" and case["max_nodes"] is None:
+        assert st["spilled"] >= p["hubs"], st
+
+
+@pytest.mark.parametrize("gi", range(len(SHAPES)), ids=[g["id"] for g, _, _, _ in SHAPES])
+def test_shapes_against_the_reference(gi, monkeypatch):
+    """Index.from_arrays(...).subgraphs and the drop-in kmers.get_subgraphs on every shape case: subgraphs in final order, used,
+    element types, rng state, induced edges and used hashes against the goldens, and the kernel paths reached."""
+    from seqwin_amd import kmers
+    from seqwin_amd.device import Index
+    _hooks(monkeypatch)
+    g, nodes, edges, cases = SHAPES[gi]
+    ix = Index.from_arrays(nodes, edges)
+    for case, exp in cases:
+        want = case["error"] or case["csr_sha256"]
+        sg, after = _run_shape(ix, case)
+        assert after == case["rng_after"], case
+        if case["error"]:
+            assert sg == case["error"]
+        else:
+            sgs, used = sg.as_reference()
+            _check_types(sgs, used)
+            assert _digest(sg) == want, case
+            if exp is not None:
+                assert _np_sets(sgs) == H.csr_to_sets(*exp), case
+            offs, hashes = sg.csr()
+            assert len(used) == case["n_used"] == len(hashes) and frozenset(int(x) for x in used) == frozenset(hashes.tolist())
+            assert np.array_equal(sg.used_hashes(), np.sort(hashes))
+            assert sg.used_mask().sum() == case["n_used"]
+            _induced_grouped_ok(sg, nodes, edges)
+            if case["n_subgraphs"] <= 300:
+                _induced_ok(sg, nodes, edges)
+            _shape_paths(g, case, sg.stats())
+            sg.close()
+        rng = random.Random(case["seed"])
+        try:
+            got = kmers.get_subgraphs(nodes, edges, case["penalty_th"], case["min_nodes"], case["max_nodes"], rng)
+            _check_types(*got)
+            got = S.csr_digest(*S.canonical_csr(got[0]))
+        except RuntimeError as e:
+            got = str(e)
+        assert got == want and rng.random() == case["rng_after"], ("dropin", case)
+    ix.close()
+
+
+def _shape(family, **params):
+    return next(s for s in SHAPES if s[0]["family"] == family and all(s[0]["params"].get(k) == v for k, v in params.items()))
+
+
+@pytest.mark.parametrize("family", ["many_seeds", "dense"])
+def test_window_sizes_give_one_result(family, monkeypatch):
+    from seqwin_amd.device import Index
+    g, nodes, edges, cases = _shape(family)
+    case = cases[0][0]
+    ix = Index.from_arrays(nodes, edges)
+    for w in (1, 63, 64, 65, 255, 256, 257, 1000, 4095, 4096, 10000):
+        _hooks(monkeypatch, WINDOW=w)
+        sg, after = _run_shape(ix, case)
+        assert _digest(sg) == case["csr_sha256"] and after == case["rng_after"], w
+        st = sg.stats()
+        assert st["window"] == min(w, 4096) and st["kept"] + st["discarded"] + st["skipped_used"] == st["seeds"], (w, st)
+        if w == 1:
+            # one expansion per round; a last round may find only used seeds left and expand nothing
+            assert st["invalidated"] == 0 and st["expansions"] <= st["rounds"] <= st["expansions"] + 1, st
+        sg.close()
+    ix.close()
+
+
+@pytest.mark.parametrize("deg", [1024, 1025, 2048])
+def test_lds_frontier_caps_give_one_result(deg, monkeypatch):
+    from seqwin_amd.device import Index
+    g, nodes, edges, cases = _shape("star", deg=deg)
+    ix = Index.from_arrays(nodes, edges)
+    for cap in (1, 63, 64, 65, 1023):
+        _hooks(monkeypatch, LDS_CAP=cap)
+        for case, _ in cases:
+            sg, after = _run_shape(ix, case)
+            assert _digest(sg) == case["csr_sha256"] and after == case["rng_after"], (cap, case)
+            assert sg.stats()["spilled"] >= 1
+            sg.close()
+    ix.close()
+
+
+def test_long_components_spill_once_each(monkeypatch):
+    """Window 1: exactly one spill per component that an expansion takes beyond the 128 LDS subgraph entries."""
+    from seqwin_amd.device import Index
+    g, nodes, edges, cases = _shape("long")
+    big = 3 * sum(s >= 129 for s in g["params"]["sizes"])
+    ix = Index.from_arrays(nodes, edges)
+    _hooks(monkeypatch, WINDOW=1)
+    for case, _ in cases:
+        sg, after = _run_shape(ix, case)
+        assert _digest(sg) == case["csr_sha256"] and after == case["rng_after"], case
+        mx = case["max_nodes"]
+        st = sg.stats()
+        assert st["spilled"] == (big if mx is None or mx > 128 else 0), (case, st)
+        sg.close()
+    _hooks(monkeypatch, WINDOW=1, LDS_CAP=64)   # the cliques' frontiers spill too, the paths' do not
+    sg, _ = _run_shape(ix, cases[0][0])
+    assert _digest(sg) == cases[0][0]["csr_sha256"]
+    ix.close()
+
+
+def test_multiple_spills_with_invalidation(monkeypatch):
+    from seqwin_amd.device import Index
+    g, nodes, edges, cases = _shape("multi_spill")
+    ix = Index.from_arrays(nodes, edges)
+    for env in ({}, {"WINDOW": 1}, {"WINDOW": 4096}):
+        _hooks(monkeypatch, **env)
+        for case, _ in cases:
+            sg, after = _run_shape(ix, case)
+            st = sg.stats()
+            assert _digest(sg) == case["csr_sha256"] and after == case["rng_after"], (env, case)
+            assert st["spilled"] >= g["params"]["hubs"], (env, st)
+            if env.get("WINDOW") == 4096:
+                assert st["invalidated"] > 0, st
+            sg.close()
+    ix.close()
+
+
+def test_filter_chain_at_scale():
+    """filter_graph, subgraphs and filter_kmers on the bench generator's graph (512 genomes, 30 ancestors, penalty_th 0.2)
+    against the numpy expressions of kmers._filter_edges_and_nodes, the host restatement and the oracle's filter_kmers."""
+    import oracle
+    from seqwin_amd.device import Batch
+    G, th = 512, 0.2
+    b = Batch.synthetic(G, 50, 100_000, n_ancestors=30, snp_ppm=10_000, seed=1)
+    tar = [g % 30 == 0 for g in range(G)]
+    n_tar = sum(tar)
+    ix = b.build_index(21, 200, tar)
+    ewt = 0.3 * (1 - th) * n_tar
+    k_all, nodes, edges = ix.export()
+    e_want = edges[edges["weight"] > np.uintp(ewt)]
+    keep = np.unique(e_want.view(np.uint64).reshape(-1, 3)[:, :2])
+    n_want = nodes[np.searchsorted(nodes["hash"], keep)]
+    f = ix.filter_graph(ewt)
+    _, fn, fe = f.export()
+    assert len(fn) > 1_000_000 and np.array_equal(fn, n_want) and np.array_equal(fe, e_want)
+    rs = random.Random(1)
+    want = H.get_subgraphs(fn, fe, th, 3, 100, rs)
+    rng = random.Random(1)
+    sg = f.subgraphs(th, 3, 100, rng)
+    got = sg.as_reference()
+    assert _np_sets(got[0]) == want[0] and got[1] == want[1] and rng.random() == rs.random()
+    st = sg.stats()
+    assert st["kept"] == len(want[0]) > 1000 and st["kept"] + st["discarded"] + st["skipped_used"] == st["seeds"]
+    gk, gn, _ = ix.filter_kmers(f, sg).export()
+    ek, en = oracle.filter_kmers(k_all, fn, sg.used_hashes())
+    assert np.array_equal(gk, ek) and np.array_equal(gn, en) and len(en) == len(want[1])
+    sg.close()
+
+
+def test_release_library_shapes():
+    """The release library (test hooks compiled out) through the drop-in on the many-seeds and rounding shapes."""
+    code = (
+        "import random, sys\n"
+        "sys.path.insert(0, 'tests/tools')\n"
+        "import sg_shapes as S\n"
+        "from seqwin_amd._lib import LIB_PATH\n"
+        "from seqwin_amd import kmers\n"
+        "assert str(LIB_PATH).endswith('libseqwin_hip.so'), LIB_PATH\n"
+        "n = 0\n"
+        "for g, nodes, edges, cases in S.load_golden('tests/golden', families=('many_seeds', 'rounding')):\n"
+        "    for case, _ in cases:\n"
+        "        rng = random.Random(case['seed'])\n"
+        "        sgs, used = kmers.get_subgraphs(nodes, edges, case['penalty_th'], case['min_nodes'], case['max_nodes'], rng)\n"
+        "        assert S.csr_digest(*S.canonical_csr(sgs)) == case['csr_sha256'], (g['id'], case)\n"
+        "        assert rng.random() == case['rng_after']\n"
+        "        n += 1\n"
+        "print('release ok', n)\n")
+    env = {k: v for k, v in os.environ.items() if k not in ("SEQWIN_AMD_LIB",) + SG_HOOKS}
+    env["SEQWIN_AMD_RELEASE_LIB"] = "1"
+    r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, cwd=str(ROOT), env=env, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    n = sum(len(cs) for g, _, _, cs in SHAPES if g["family"] in ("many_seeds", "rounding"))
+    assert f"release ok {n}" in r.stdout, r.stdout
