@@ -267,6 +267,13 @@ void radix_layout(unsigned bits, unsigned *digit_bits, unsigned *n_passes);
 // keys[i] >> 32 a permutation of 0 .. n-1: grouped by the index bits [low_bits, nbit) in two unstable passes (false: not taken)
 bool radix_unsort_perm(uint64_t *&keys, uint64_t *&alt, uint64_t n, unsigned low_bits, unsigned nbit, hipStream_t stream, uint32_t *d_fail);
 
+// the edge keys by two unstable bucket passes and an LDS finish per sub-bucket (radix.hip): 0 = ukeys / ucnt / *n_runs written as
+// k_rle_keys + k_drop_sentinel_run leave them, 1 = not done (a sub-bucket above `cap` keys or `slots` distinct keys): `keys`
+// still holds the same multiset and the caller sorts it by radix passes.  Synchronises the stream.
+int radix_edge_buckets(uint64_t *&keys, uint64_t *&alt, uint64_t m, unsigned key_bits, uint64_t sentinel,
+                       const unsigned long long *d_hist_top, uint32_t cap, uint32_t slots, uint64_t *ukeys, uint32_t *ucnt,
+                       uint32_t *n_runs, hipStream_t stream, uint32_t *d_fail, bool debug);
+
 // index.hip: radix.hip or rocPRIM; d_fail: zeroed device word, to be read back and handed to check_sort_failed
 void sort_keys64(uint64_t *&keys, uint64_t *&keys_alt, size_t n, unsigned begin_bit, unsigned end_bit, hipStream_t stream,
                  uint32_t *d_fail, bool perm_hi32 = false, unsigned long long *d_hist_given = nullptr, unsigned layout_bits = 0);

@@ -3165,6 +3165,10 @@ namespace {
 // the run lengths give the number of records of every pair; the candidates (records that may repeat their pair inside one
 // assembly: ck / ca, *d_n_cand of them, unordered) are sorted by (pair, assembly) and the repeats taken off.
 // (d_n_cand == nullptr: the caller knows the number of candidates, host_n_cand.)
+// the bucket route of the edge keys (radix_edge_buckets): from this many keys on, at most EDGE_BUCKET_CAP keys in a sub-bucket
+// (one workgroup streams them: a bound on the longest workgroup, 8 MB), EDGE_BUCKET_SLOTS LDS slots for a sub-bucket's distinct keys
+constexpr uint64_t EDGE_BUCKET_MIN_KEYS = 1ull << 26;
+constexpr uint32_t EDGE_BUCKET_CAP = 1u << 20, EDGE_BUCKET_SLOTS = 4096;
 struct WideKeys {   // multi-GPU slices: key = (rank_lo - lo_base) << hi_bits | rank_hi, hashes through the per-owner table
     unsigned lo_bits, hi_bits;
     uint64_t lo_base;
@@ -3200,10 +3204,6 @@ void edges_from_pairs(uint64_t *keys, uint64_t *keys_alt, uint64_t m, uint64_t s
         skip = std::min(skip, n_passes - 1);
         low_bits = skip * digit_bits;
     }
-    sort_keys64(keys, keys_alt, m, low_bits, key_bits, stream, sort_fail.p, false,
-                d_hist ? d_hist + ((size_t)skip << digit_bits) : nullptr, key_bits);   // (d_hist: the digit counts k_adj_pairs took)
-    RepairState rep;
-    if (low_bits) enqueue_repair(EdgeKeyView{keys, low_bits}, EdgeKeyView{keys, low_bits}, ~0ull, m, nullptr, 0, rep, stream);
     DevArray<uint64_t> ukeys(m);
     DevArray<uint32_t> ucnt(m + 1), ucount(2);   // ucount[1]: places where the sorted keys descend (order guard, r05)
     unsigned long long n_cand = host_n_cand;
@@ -3211,8 +3211,38 @@ void edges_from_pairs(uint64_t *keys, uint64_t *keys_alt, uint64_t m, uint64_t s
     // SEQWIN_AMD_RLE=rocprim: rocprim::run_length_encode (ucnt = the lengths) -- A/B, and what rounds 1-3 ran
     const char *rle_env = SW_AB_GETENV("SEQWIN_AMD_RLE");   // (-DSW_AB builds only)
     const bool own_rle = !(rle_env && !strcmp(rle_env, "rocprim"));
+    // r07: where every pair has many copies, the keys are grouped by two unstable bucket passes and each sub-bucket is finished in
+    // LDS (radix_edge_buckets: no sorted key array, no repair, no run-length pass) -- the packed single-device form, from
+    // EDGE_BUCKET_MIN_KEYS keys on and above four keys per node (below, few pairs repeat: the LDS tables of distinct keys overflow
+    // and the second skipped digit pays instead, see `skip`).  A sub-bucket beyond the capacities sends the untouched multiset down the radix passes.
+    bool by_buckets = !wide && nb < 32 && own_rle && sort_keys64_is_own(m) && m >= EDGE_BUCKET_MIN_KEYS && ix.n_nodes && m > 4 * ix.n_nodes;
+    uint32_t bucket_cap = EDGE_BUCKET_CAP, bucket_slots = EDGE_BUCKET_SLOTS;
+    if (const char *e = SW_TEST_GETENV("SEQWIN_AMD_EDGE_SORT")) by_buckets = !wide && nb < 32 && own_rle && !strcmp(e, "bucket");   // tests: either route at any size
+    if (const char *e = SW_TEST_GETENV("SEQWIN_AMD_EDGE_BUCKET_CAP")) bucket_cap = (uint32_t)strtoul(e, nullptr, 10);
+    if (const char *e = SW_TEST_GETENV("SEQWIN_AMD_EDGE_BUCKET_SLOTS")) bucket_slots = (uint32_t)strtoul(e, nullptr, 10);
+    if (by_buckets) {
+        unsigned db = 0, np = 0;
+        radix_layout(key_bits, &db, &np);
+        uint32_t n_runs = 0;
+        by_buckets = radix_edge_buckets(keys, keys_alt, m, key_bits, sentinel, d_hist ? d_hist + ((size_t)(np - 1) << db) : nullptr, bucket_cap,
+                                        bucket_slots, ukeys.p, ucnt.p, &n_runs, stream, sort_fail.p,
+                                        getenv("SEQWIN_AMD_DEBUG_EDGE_REPAIR") != nullptr) == 0;
+        if (by_buckets) {
+            uint32_t failed = 0;
+            SW_HIP(hipMemcpyAsync(&failed, sort_fail.p, 4, hipMemcpyDeviceToHost, stream));
+            if (d_n_cand) SW_HIP(hipMemcpyAsync(&n_cand, d_n_cand, 8, hipMemcpyDeviceToHost, stream));
+            SW_HIP(hipStreamSynchronize(stream));
+            check_sort_failed(failed);
+            ix.n_edges = n_runs;
+        }
+    }
+    if (!by_buckets)
+        sort_keys64(keys, keys_alt, m, low_bits, key_bits, stream, sort_fail.p, false,
+                    d_hist ? d_hist + ((size_t)skip << digit_bits) : nullptr, key_bits);   // (d_hist: the digit counts k_adj_pairs took)
+    RepairState rep;
+    if (low_bits && !by_buckets) enqueue_repair(EdgeKeyView{keys, low_bits}, EdgeKeyView{keys, low_bits}, ~0ull, m, nullptr, 0, rep, stream);
     bool demoted = false;
-    for (int attempt = 0;; ++attempt) {
+    for (int attempt = 0; !by_buckets; ++attempt) {
         SW_HIP(hipMemsetAsync(ucount.p + 1, 0, 4, stream));
         if (own_rle) {
             const unsigned blocks = (unsigned)((m + RLE_TILE - 1) / RLE_TILE);

@@ -108,6 +108,15 @@ constexpr unsigned long long RS_AGG = 1ull << 62, RS_INC = 2ull << 62, RS_VAL = 
 // Lanes of the wave whose digit equals this lane's (among the live ones), as two 32-bit halves: per digit bit one ballot and,
 // per half, one three-input bit operation  m & ~(ballot ^ -bit)  (the compiler's own form of  m &= bit ? bal : ~bal  was nine
 // VALU instructions per bit on 64-bit lane masks -- 107 per key at 9 bits, a third of a pass).
+// table word of a SEG pass (k_rs_pass_p): first key << 24 | bucket << 15 | number of keys (at most 2^14, a tile)
+__host__ __device__ __forceinline__ unsigned long long seg_pack(uint64_t first, uint32_t bucket, uint32_t count)
+{
+    return (unsigned long long)first << 24 | (unsigned long long)bucket << 15 | count;
+}
+__device__ __forceinline__ uint64_t seg_first(unsigned long long w) { return w >> 24; }
+__device__ __forceinline__ uint32_t seg_bucket(unsigned long long w) { return (uint32_t)(w >> 15) & 0x1FFu; }
+__device__ __forceinline__ uint32_t seg_count(unsigned long long w) { return (uint32_t)w & 0x7FFFu; }
+
 template <int BITS>
 __device__ __forceinline__ void match_digit(uint32_t d, bool live, uint32_t &mlo, uint32_t &mhi)
 {
@@ -376,7 +385,11 @@ __device__ __forceinline__ uint32_t rse_flag(unsigned long long w, uint32_t epoc
 // one instruction that hit the same word are served in ascending lane order.  The second is not an architectural promise, so
 // it is CHECKED on the device before the first sort (contended patterns under full occupancy, every rank compared with the
 // ballot form's); a device that fails keeps RANK = 0.  The unstable passes (atomic cursors) need neither property.
-template <int THREADS, int BITS, int RANK>
+//
+// SEG (an unstable pass inside buckets whose sizes are data: the second level of radix_edge_buckets): work item `tile` is not
+// the range [tile * TILE, ...) but what digit_base[tile] says -- seg_pack(first key, bucket, number of keys) --, so a tile
+// never straddles two buckets and the buckets need no padding; the bucket is the cursor group.
+template <int THREADS, int BITS, int RANK, bool SEG = false>
 __global__ __launch_bounds__(THREADS) void k_rs_pass_p(const uint64_t *__restrict__ in, uint64_t *__restrict__ out, uint64_t n,
                                                        uint32_t n_tiles, unsigned shift, unsigned bits,
                                                        const unsigned long long *__restrict__ digit_base,
@@ -400,10 +413,17 @@ __global__ __launch_bounds__(THREADS) void k_rs_pass_p(const uint64_t *__restric
     uint32_t tile = s_tile;
     uint64_t key[RS_ITEMS];
     uint32_t rank[RS_ITEMS];
+    unsigned long long seg = 0, nseg = 0;   // (SEG) this tile's and the next one's table word
+    if constexpr (SEG) seg = tile < n_tiles ? digit_base[tile] : 0ull;
 #pragma unroll
     for (int i = 0; i < RS_ITEMS; ++i) {
-        const uint64_t g = (uint64_t)tile * TILE + wave * (64 * RS_ITEMS) + i * 64 + lane;
-        key[i] = (tile < n_tiles && g < n) ? in[g] : ~0ull;
+        const uint32_t li = wave * (64 * RS_ITEMS) + i * 64 + lane;
+        if constexpr (SEG) {
+            key[i] = li < seg_count(seg) ? in[seg_first(seg) + li] : ~0ull;
+        } else {
+            const uint64_t g = (uint64_t)tile * TILE + li;
+            key[i] = (tile < n_tiles && g < n) ? in[g] : ~0ull;
+        }
     }
     const uint32_t tid0 = threadIdx.x;
     // The ticket of the tile AFTER the next is taken while the next tile's keys are requested (r04: taken at the top of an
@@ -422,7 +442,7 @@ __global__ __launch_bounds__(THREADS) void k_rs_pass_p(const uint64_t *__restric
         for (uint32_t i = tid; i < WAVES * RADIX / 2; i += THREADS) (reinterpret_cast<uint32_t *>(&whist[0][0]))[i] = 0;
         __syncthreads();
         const uint64_t t0 = (uint64_t)tile * TILE;
-        const uint32_t cnt_tile = (uint32_t)min((uint64_t)TILE, n - t0);
+        const uint32_t cnt_tile = SEG ? seg_count(seg) : (uint32_t)min((uint64_t)TILE, n - t0);
         if constexpr (RANK == 1) {
             // all sixteen atomics are issued before the first result is looked at (the LDS unit serves a wave's instructions in
             // order, so the results are the ranks whatever the wave waits for): one exposed LDS round trip instead of sixteen
@@ -487,7 +507,7 @@ __global__ __launch_bounds__(THREADS) void k_rs_pass_p(const uint64_t *__restric
                 // digit's range with one atomic add -- no states, no look-back; the answer is due after the keys sit in LDS
                 // (group_shift < 64: the cursors of the range of 2^group_shift positions the tile lies in -- a pass inside the buckets
                 //  an earlier pass made, see radix_unsort_perm)
-                const uint64_t group = group_shift < 64u ? (((uint64_t)tile * TILE) >> group_shift) : 0ull;
+                const uint64_t group = SEG ? seg_bucket(seg) : group_shift < 64u ? (((uint64_t)tile * TILE) >> group_shift) : 0ull;
                 pre[0] = total ? atomicAdd(&cursor[(group * RADIX + d) * cursor_stride], (unsigned long long)total) : 0ull;
             } else {
                 __hip_atomic_store(&st[d], rse_pack(epoch, tile == 0 ? 2u : 1u, total), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -515,6 +535,7 @@ __global__ __launch_bounds__(THREADS) void k_rs_pass_p(const uint64_t *__restric
         if (tid == 0) s_tile = fut;
         __syncthreads();
         const uint32_t ntile = s_tile;
+        if constexpr (SEG) nseg = ntile < n_tiles ? digit_base[ntile] : 0ull;
         // the tile in digit order, in LDS; then the next tile's keys are requested into the same registers (in flight during the
         // write-out) and thread 0 takes the ticket after that one
         auto place_and_fetch = [&]() {
@@ -528,8 +549,13 @@ __global__ __launch_bounds__(THREADS) void k_rs_pass_p(const uint64_t *__restric
             }
 #pragma unroll
             for (int i = 0; i < RS_ITEMS; ++i) {
-                const uint64_t g = (uint64_t)ntile * TILE + wave * (64 * RS_ITEMS) + i * 64 + lane;
-                key[i] = (ntile < n_tiles && g < n && !(dbg & 4u)) ? in[g] : (dbg & 4u ? g * 0x9E3779B97F4A7C15ull : ~0ull);
+                const uint32_t li = wave * (64 * RS_ITEMS) + i * 64 + lane;
+                if constexpr (SEG) {
+                    key[i] = li < seg_count(nseg) ? in[seg_first(nseg) + li] : ~0ull;
+                } else {
+                    const uint64_t g = (uint64_t)ntile * TILE + li;
+                    key[i] = (ntile < n_tiles && g < n && !(dbg & 4u)) ? in[g] : (dbg & 4u ? g * 0x9E3779B97F4A7C15ull : ~0ull);
+                }
             }
             if (tid == 0) fut = atomicAdd(ticket, 1u);
         };
@@ -619,6 +645,7 @@ __global__ __launch_bounds__(THREADS) void k_rs_pass_p(const uint64_t *__restric
         RS_STAMP(7);   // stores issued
         // (no barrier here: the next iteration touches sk / goff / s_tile only behind its own barriers)
         tile = ntile;
+        seg = nseg;
     }
 }
 
@@ -1393,6 +1420,402 @@ void radix_sort_pairs32(uint32_t *&keys, uint32_t *&keys_alt, OccPay *&vals, Occ
         std::swap(keys, keys_alt);
         std::swap(vals, vals_alt);
     }
+}
+
+// ---- the edge keys by buckets (r07): two unstable passes, most significant digit first, then every bucket finished in LDS ----
+// keys = (rank_lo << nb) | rank_hi of every adjacency record plus one `sentinel` (all key bits set) per record boundary.  Only the
+// DISTINCT keys in ascending order and the start of every run of equal keys are wanted, equal keys are indistinguishable (no
+// stability needed) and every key has several copies.  Level 1 groups by the top digit of radix_layout(key_bits) (its counts
+// come from the producer of the keys), level 2 by the nine bits below; both claim their places from cursors like the unsort's
+// passes.  A sweep over the level-1 output counts level 2 (per tile an LDS histogram, flushed with one global atomic per
+// non-empty bin).  k_eb_finish then takes one sub-bucket per workgroup: the keys are streamed ONCE into an LDS hash table of
+// (key, copies) -- the bucket itself never sits in LDS, so its size is bounded by patience, not by LDS --, the distinct keys are
+// binned on their next nine bits, and a key's place is its bin's start plus the number of smaller keys in its bin (bins hold two
+// or three distinct keys; a hub node's bin costs its square, bounded by the table size).  Distinct keys and run starts go to the
+// bucket's own range of a scratch pair, and k_eb_compact moves them to their run numbers (prefix over the buckets' distinct counts).
+// Nothing here ranks by lane order, and no workgroup waits for another.
+namespace {
+constexpr uint32_t EB_RADIX = 512, EB_TABLE = EB_RADIX * EB_RADIX, EB_THREADS = 512;
+constexpr uint64_t EB_EMPTY = ~0ull;
+static_assert(EB_THREADS == EB_RADIX, "k_eb_finish: one bin per thread");
+enum : uint32_t { EB_F_OVERFLOW = 1u, EB_F_RANGE = 2u, EB_F_ORDER = 4u };
+struct EbInfo {   // device -> host after the counting sweep
+    unsigned long long n_sentinels;
+    uint32_t n_tiles2, max_bucket, flags, n_runs;
+};
+
+// one workgroup of EB_RADIX threads: level-1 cursors from the digit counts, and the tile table of the level-2 sweeps
+__global__ __launch_bounds__(EB_RADIX) void k_eb_level1(const unsigned long long *__restrict__ h1, uint32_t tile_keys,
+                                                        unsigned long long *__restrict__ cursor, unsigned long long *__restrict__ segtab,
+                                                        EbInfo *__restrict__ info)
+{
+    __shared__ unsigned long long s[EB_RADIX];
+    __shared__ uint32_t st[EB_RADIX];
+    const uint32_t d = threadIdx.x;
+    const unsigned long long c = h1[d];
+    const uint32_t tiles = (uint32_t)((c + tile_keys - 1) / tile_keys);
+    s[d] = c;
+    st[d] = tiles;
+    __syncthreads();
+    for (uint32_t o = 1; o < EB_RADIX; o <<= 1) {
+        const unsigned long long a = d >= o ? s[d - o] : 0;
+        const uint32_t b = d >= o ? st[d - o] : 0;
+        __syncthreads();
+        s[d] += a;
+        st[d] += b;
+        __syncthreads();
+    }
+    const unsigned long long first = s[d] - c;
+    cursor[(size_t)d * RS_CURSOR_STRIDE] = first;
+    uint32_t w = st[d] - tiles;
+    for (uint32_t t = 0; t < tiles; ++t)
+        segtab[w + t] = seg_pack(first + (uint64_t)t * tile_keys, d, (uint32_t)min((unsigned long long)tile_keys, c - (uint64_t)t * tile_keys));
+    if (d == EB_RADIX - 1) info->n_tiles2 = st[d];
+}
+
+// level-2 digit counts of the level-1 output: table[bucket * EB_RADIX + digit]; the sentinels are counted a second time apart
+__global__ __launch_bounds__(1024) void k_eb_count(const uint64_t *__restrict__ in, const unsigned long long *__restrict__ segtab,
+                                                   const EbInfo *__restrict__ info, unsigned shift, uint32_t dmask, uint64_t sentinel,
+                                                   uint32_t *__restrict__ table, EbInfo *__restrict__ out)
+{
+    __shared__ uint32_t hist[EB_RADIX];
+    __shared__ uint32_t s_sent;
+    const uint32_t n_tiles = info->n_tiles2;
+    for (uint32_t w = blockIdx.x; w < n_tiles; w += gridDim.x) {
+        const unsigned long long seg = segtab[w];
+        const uint64_t first = seg_first(seg);
+        const uint32_t cnt = seg_count(seg);
+        if (threadIdx.x < EB_RADIX) hist[threadIdx.x] = 0;
+        if (threadIdx.x == 0) s_sent = 0;
+        __syncthreads();
+        uint64_t key[RS_ITEMS];
+#pragma unroll
+        for (int i = 0; i < RS_ITEMS; ++i) {
+            const uint32_t li = i * 1024 + threadIdx.x;
+            key[i] = li < cnt ? in[first + li] : EB_EMPTY;
+        }
+        uint32_t sent = 0;
+#pragma unroll
+        for (int i = 0; i < RS_ITEMS; ++i) {
+            if (key[i] == EB_EMPTY) continue;
+            if (key[i] == sentinel) ++sent;
+            atomicAdd(&hist[(uint32_t)(key[i] >> shift) & dmask], 1u);
+        }
+        if (sent) atomicAdd(&s_sent, sent);
+        __syncthreads();
+        if (threadIdx.x < EB_RADIX && hist[threadIdx.x]) atomicAdd(&table[seg_bucket(seg) * EB_RADIX + threadIdx.x], hist[threadIdx.x]);
+        if (threadIdx.x == 0 && s_sent) atomicAdd(&out->n_sentinels, (unsigned long long)s_sent);
+        __syncthreads();
+    }
+}
+
+// one workgroup: start[i] = sum of cnt[< i] over the EB_TABLE sub-buckets (start[EB_TABLE] = total), the largest count -- not
+// counting the *n_sent sentinels of sub-bucket sent_at -- and, for the level-2 pass, its cursors
+__global__ __launch_bounds__(1024) void k_eb_scan(const uint32_t *__restrict__ cnt, const unsigned long long *__restrict__ n_sent,
+                                                  uint32_t sent_at, uint32_t *__restrict__ start, unsigned long long *__restrict__ cursor,
+                                                  uint32_t *__restrict__ max_out, uint32_t *__restrict__ total_out)
+{
+    constexpr uint32_t PER4 = EB_TABLE / 1024 / 4;   // a thread's 256 consecutive counts as 64 16-byte loads, sixteen in flight
+    __shared__ uint32_t ws[16], wm[16];
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+    const uint32_t sent = n_sent ? (uint32_t)*n_sent : 0u;
+    const uint4 *cnt4 = reinterpret_cast<const uint4 *>(cnt) + (size_t)tid * PER4;
+    uint32_t sum = 0, mx = 0;
+#pragma unroll 16
+    for (uint32_t j = 0; j < PER4; ++j) {
+        const uint4 c = cnt4[j];
+        mx = max(max(max(mx, c.x), max(c.y, c.z)), c.w);
+        sum += c.x + c.y + c.z + c.w;
+    }
+    if (n_sent && sent_at / (4 * PER4) == tid) {   // (the largest count leaves the sentinels out)
+        mx = 0;
+        for (uint32_t j = 0; j < 4 * PER4; ++j) {
+            const uint32_t i = tid * 4 * PER4 + j, c = cnt[i];
+            mx = max(mx, c - (i == sent_at ? min(c, sent) : 0u));
+        }
+    }
+    uint32_t incl = sum;
+    for (uint32_t o = 1; o < 64; o <<= 1) {
+        const uint32_t up = __shfl_up(incl, o, 64);
+        if (lane >= o) incl += up;
+        mx = max(mx, __shfl_xor(mx, o, 64));
+    }
+    if (lane == 63) ws[wave] = incl;
+    if (lane == 0) wm[wave] = mx;
+    __syncthreads();
+    uint32_t run = incl - sum;
+    for (uint32_t w = 0; w < wave; ++w) run += ws[w];
+    uint4 *start4 = reinterpret_cast<uint4 *>(start) + (size_t)tid * PER4;
+    ulonglong2 *cur2 = reinterpret_cast<ulonglong2 *>(cursor) + (size_t)tid * PER4 * 2;
+#pragma unroll 16
+    for (uint32_t j = 0; j < PER4; ++j) {
+        const uint4 c = cnt4[j];
+        const uint4 st = make_uint4(run, run + c.x, run + c.x + c.y, run + c.x + c.y + c.z);
+        start4[j] = st;
+        if (cursor) {
+            cur2[2 * j] = make_ulonglong2(st.x, st.y);
+            cur2[2 * j + 1] = make_ulonglong2(st.z, st.w);
+        }
+        run = st.w + c.w;
+    }
+    if (tid == 1023) {
+        start[EB_TABLE] = run;
+        if (total_out) *total_out = run;
+        uint32_t m = 0;
+        for (uint32_t w = 0; w < 16; ++w) m = max(m, wm[w]);
+        if (max_out) *max_out = m;
+    }
+}
+
+// One sub-bucket per workgroup (from the last one down: the sentinels' is the longest).  Dynamic LDS: slots x (8 + 4 + 2) bytes.
+__global__ __launch_bounds__(EB_THREADS) void k_eb_finish(const uint64_t *__restrict__ in, const uint32_t *__restrict__ start, uint32_t slots,
+                                                          unsigned shift1, unsigned shift2, uint32_t mask2, unsigned bin_shift,
+                                                          uint32_t bin_mask, uint64_t sentinel,
+                                                          uint64_t *__restrict__ tk, uint32_t *__restrict__ tc,
+                                                          uint32_t *__restrict__ n_distinct, uint32_t *__restrict__ flags)
+{
+    extern __shared__ __align__(16) unsigned char eb_lds[];
+    unsigned long long *hk = reinterpret_cast<unsigned long long *>(eb_lds);
+    uint32_t *hc = reinterpret_cast<uint32_t *>(hk + slots);
+    uint16_t *idx = reinterpret_cast<uint16_t *>(hc + slots);
+    __shared__ uint32_t bd[EB_RADIX + 1], bk[EB_RADIX], bcur[EB_RADIX], wsd[EB_THREADS / 64], wsk[EB_THREADS / 64];
+    __shared__ uint32_t s_over;
+    const uint32_t b = EB_TABLE - 1u - blockIdx.x, tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+    const uint32_t first = start[b], cnt = start[b + 1] - first;
+    if (cnt == 0) return;
+    const uint32_t mask = slots - 1u;
+    for (uint32_t s = tid; s < slots; s += EB_THREADS) {
+        hk[s] = EB_EMPTY;
+        hc[s] = 0;
+    }
+    bd[tid] = 0;
+    bk[tid] = 0;
+    if (tid == 0) s_over = 0;
+    __syncthreads();
+    uint32_t bad = 0;
+    for (uint32_t j0 = 0; j0 < cnt; j0 += 4 * EB_THREADS) {
+        if (*(volatile uint32_t *)&s_over) break;
+        uint64_t key[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const uint32_t j = j0 + i * EB_THREADS + tid;
+            key[i] = j < cnt ? in[(uint64_t)first + j] : sentinel;
+        }
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            uint64_t k = key[i];
+            bool live = k != sentinel;
+            if (live && ((uint32_t)(k >> shift1) * EB_RADIX + ((uint32_t)(k >> shift2) & mask2)) != b) {
+                bad = 1;
+                live = false;
+            }
+            // the copies of the wave's first key go in as one (a hub node's pair fills whole waves)
+            uint32_t copies = 1;
+            const uint64_t any = __ballot(live);
+            if (any) {
+                const int src = __ffsll((long long)any) - 1;
+                const uint64_t k0 = (uint64_t)__shfl((unsigned long long)k, src, 64);
+                const uint64_t same = __ballot(live && k == k0);
+                if (live && k == k0) {
+                    copies = (uint32_t)__popcll(same);
+                    live = (int)lane == src;
+                }
+            }
+            if (!live) continue;
+            uint32_t h = (uint32_t)((k * 0x9E3779B97F4A7C15ull) >> 40) & mask, probes = 0;
+            for (; probes < slots; ++probes) {
+                const unsigned long long old = atomicCAS(&hk[h], EB_EMPTY, (unsigned long long)k);
+                if (old == EB_EMPTY || old == k) {
+                    atomicAdd(&hc[h], copies);
+                    break;
+                }
+                h = (h + 1u) & mask;
+            }
+            if (probes == slots) s_over = 1;
+        }
+    }
+    if (bad) atomicOr(flags, EB_F_RANGE);
+    __syncthreads();
+    if (s_over) {   // more distinct keys than slots: the caller sorts the untouched multiset by radix passes
+        if (tid == 0) atomicOr(flags, EB_F_OVERFLOW);
+        return;
+    }
+    // distinct keys and copies per bin
+    for (uint32_t s = tid; s < slots; s += EB_THREADS) {
+        const uint64_t k = hk[s];
+        if (k == EB_EMPTY) continue;
+        const uint32_t bin = (uint32_t)(k >> bin_shift) & bin_mask;
+        atomicAdd(&bd[bin], 1u);
+        atomicAdd(&bk[bin], hc[s]);
+    }
+    __syncthreads();
+    {   // exclusive scans over the EB_RADIX bins (one bin per thread)
+        const uint32_t d = bd[tid], c = bk[tid];
+        uint32_t id = d, ic = c;
+        for (uint32_t o = 1; o < 64; o <<= 1) {
+            const uint32_t ud = __shfl_up(id, o, 64), uc = __shfl_up(ic, o, 64);
+            if (lane >= o) {
+                id += ud;
+                ic += uc;
+            }
+        }
+        if (lane == 63) {
+            wsd[wave] = id;
+            wsk[wave] = ic;
+        }
+        __syncthreads();
+        uint32_t pd = id - d, pc = ic - c;
+        for (uint32_t w = 0; w < wave; ++w) {
+            pd += wsd[w];
+            pc += wsk[w];
+        }
+        bd[tid] = pd;
+        bcur[tid] = pd;
+        bk[tid] = pc;
+        if (tid == EB_THREADS - 1) bd[EB_RADIX] = pd + d;
+    }
+    __syncthreads();
+    for (uint32_t s = tid; s < slots; s += EB_THREADS) {
+        const uint64_t k = hk[s];
+        if (k == EB_EMPTY) continue;
+        idx[atomicAdd(&bcur[(uint32_t)(k >> bin_shift) & bin_mask], 1u)] = (uint16_t)s;
+    }
+    __syncthreads();
+    const uint32_t n_dist = bd[EB_RADIX];
+    if (tid == 0) n_distinct[b] = n_dist;
+    for (uint32_t j = tid; j < n_dist; j += EB_THREADS) {
+        const uint32_t s = idx[j];
+        const uint64_t k = hk[s];
+        const uint32_t bin = (uint32_t)(k >> bin_shift) & bin_mask, lo = bd[bin], hi = bd[bin + 1];
+        uint32_t less = 0, copies_less = 0;
+        for (uint32_t i = lo; i < hi; ++i) {
+            const uint32_t s2 = idx[i];
+            if (hk[s2] < k) {
+                ++less;
+                copies_less += hc[s2];
+            }
+        }
+        tk[(uint64_t)first + lo + less] = k;
+        tc[(uint64_t)first + lo + less] = first + bk[bin] + copies_less;
+    }
+}
+
+// distinct keys and run starts from the buckets' own ranges to their run numbers; the order check where the data is in hand
+__global__ __launch_bounds__(256) void k_eb_compact(const uint64_t *__restrict__ tk, const uint32_t *__restrict__ tc,
+                                                    const uint32_t *__restrict__ start, const uint32_t *__restrict__ dstart,
+                                                    const unsigned long long *__restrict__ n_sentinels, uint64_t *__restrict__ ukeys,
+                                                    uint32_t *__restrict__ ucnt, uint32_t *__restrict__ flags)
+{
+    const uint32_t b = blockIdx.x, d0 = dstart[b], n = dstart[b + 1] - d0;
+    if (b == EB_TABLE - 1u && threadIdx.x == 0) ucnt[dstart[EB_TABLE]] = start[EB_TABLE] - (uint32_t)*n_sentinels;
+    if (n == 0) return;
+    const uint64_t first = start[b];
+    uint32_t bad = 0;
+    for (uint32_t j = threadIdx.x; j < n; j += 256) {
+        const uint64_t k = tk[first + j];
+        const uint32_t c = tc[first + j];
+        if (j + 1 < n && (tk[first + j + 1] <= k || tc[first + j + 1] <= c)) bad = 1;
+        if (c < first || c >= start[b + 1]) bad = 1;
+        ukeys[d0 + j] = k;
+        ucnt[d0 + j] = c;
+    }
+    if (bad) atomicOr(flags, EB_F_ORDER);
+}
+}  // namespace
+
+// 0: ukeys[0, *n_runs) / ucnt[0, *n_runs] hold the distinct real keys and their run starts (ucnt[*n_runs] = number of real keys);
+// 1: not done -- `keys` still holds the same multiset (in some order), the caller sorts it by radix passes.
+// d_hist_top: the counts of the top digit of radix_layout(key_bits) (nullptr: counted here); cap: most real keys in a sub-bucket;
+// slots: size of the LDS table of distinct keys (a power of two, at most 8192).
+int radix_edge_buckets(uint64_t *&keys, uint64_t *&alt, uint64_t m, unsigned key_bits, uint64_t sentinel,
+                       const unsigned long long *d_hist_top, uint32_t cap, uint32_t slots, uint64_t *ukeys, uint32_t *ucnt,
+                       uint32_t *n_runs, hipStream_t stream, uint32_t *d_fail, bool debug)
+{
+    constexpr int THREADS = 1024, BITS = 9;
+    constexpr uint32_t TILE = THREADS * RS_ITEMS;
+    unsigned digit_bits = 0, n_passes = 0;
+    radix_layout(key_bits, &digit_bits, &n_passes);
+    if (n_passes < 2 || m >= (1ull << 32) - 1 || slots < 64 || slots > 8192 || (slots & (slots - 1))) return 1;
+    const unsigned shift1 = (n_passes - 1) * digit_bits, bits1 = key_bits - shift1;          // level 1: the layout's top digit
+    const unsigned bits2 = std::min<unsigned>(BITS, shift1), shift2 = shift1 - bits2;          // level 2: the nine bits below
+    const unsigned bin_bits = std::min<unsigned>(BITS, shift2), bin_shift = shift2 - bin_bits;  // the finish kernel's bins
+    const uint64_t n_tiles = (m + TILE - 1) / TILE, max_tiles2 = n_tiles + EB_RADIX;
+    int dev = 0, per_cu = 0;
+    SW_HIP(hipGetDevice(&dev));
+    hipDeviceProp_t prop;
+    SW_HIP(hipGetDeviceProperties(&prop, dev));
+    SW_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_rs_pass_p<THREADS, BITS, 0>, THREADS, 0));
+    const unsigned cus = (unsigned)std::max(1, prop.multiProcessorCount);
+    const unsigned grid = (unsigned)std::min<uint64_t>(n_tiles, (uint64_t)std::max(1, per_cu) * cus);
+
+    DevArray<unsigned long long> h1(EB_RADIX), cur1((size_t)EB_RADIX * RS_CURSOR_STRIDE), cur2(EB_TABLE), segtab(max_tiles2);
+    DevArray<uint32_t> table(EB_TABLE), start(EB_TABLE + 1), tickets(2), flags(1);
+    DevArray<EbInfo> info(1);
+    SW_HIP(hipMemsetAsync(h1.p, 0, h1.bytes(), stream));
+    SW_HIP(hipMemsetAsync(table.p, 0, table.bytes(), stream));
+    SW_HIP(hipMemsetAsync(tickets.p, 0, 8, stream));
+    SW_HIP(hipMemsetAsync(flags.p, 0, 4, stream));
+    SW_HIP(hipMemsetAsync(info.p, 0, sizeof(EbInfo), stream));
+    if (d_hist_top)
+        SW_HIP(hipMemcpyAsync(h1.p, d_hist_top, (size_t)8 << digit_bits, hipMemcpyDeviceToDevice, stream));
+    else
+        hipLaunchKernelGGL(k_rs_hist<BITS>, dim3((unsigned)((m + 32767) / 32768)), dim3(256), 0, stream, (const uint64_t *)keys, m, shift1,
+                           key_bits, 1u, h1.p);
+    hipLaunchKernelGGL(k_eb_level1, dim3(1), dim3(EB_RADIX), 0, stream, (const unsigned long long *)h1.p, TILE, cur1.p, segtab.p, info.p);
+    auto pass1 = ballot_forced() ? k_rs_pass_p<THREADS, BITS, 0> : k_rs_pass_p<THREADS, BITS, 1>;
+    hipLaunchKernelGGL(pass1, dim3(grid), dim3(THREADS), 0, stream, (const uint64_t *)keys, alt, m, (uint32_t)n_tiles, shift1, bits1,
+                       (const unsigned long long *)nullptr, (unsigned long long *)nullptr, tickets.p, d_fail, 0u, cur1.p, RS_CURSOR_STRIDE,
+                       64u, 0u);
+    std::swap(keys, alt);
+    hipLaunchKernelGGL(k_eb_count, dim3((unsigned)std::min<uint64_t>(max_tiles2, (uint64_t)8 * cus)), dim3(1024), 0, stream,
+                       (const uint64_t *)keys, (const unsigned long long *)segtab.p, (const EbInfo *)info.p, shift2, (1u << bits2) - 1u,
+                       sentinel, table.p, info.p);
+    const uint32_t sent_at = (uint32_t)(sentinel >> shift1) * EB_RADIX + ((uint32_t)(sentinel >> shift2) & ((1u << bits2) - 1u));
+    hipLaunchKernelGGL(k_eb_scan, dim3(1), dim3(1024), 0, stream, (const uint32_t *)table.p, (const unsigned long long *)&info.p->n_sentinels,
+                       sent_at, start.p, cur2.p, &info.p->max_bucket, (uint32_t *)nullptr);
+    SW_HIP(hipGetLastError());
+    EbInfo hi;
+    SW_HIP(hipMemcpyAsync(&hi, info.p, sizeof hi, hipMemcpyDeviceToHost, stream));
+    SW_HIP(hipStreamSynchronize(stream));
+    if (debug)
+        fprintf(stderr, "[edge buckets] %llu keys, %llu sentinels, digits %u+%u+%u of %u bits, largest sub-bucket %u (capacity %u, %u slots)%s\n",
+                (unsigned long long)m, hi.n_sentinels, bits1, bits2, bin_bits, key_bits, hi.max_bucket, cap, slots,
+                hi.max_bucket > cap ? ": radix passes instead" : "");
+    if (hi.max_bucket > cap) return 1;   // (the keys are the level-1 output: the same multiset)
+    auto pass2 = ballot_forced() ? k_rs_pass_p<THREADS, BITS, 0, true> : k_rs_pass_p<THREADS, BITS, 1, true>;
+    hipLaunchKernelGGL(pass2, dim3(std::max(1u, std::min(hi.n_tiles2, (uint32_t)(std::max(1, per_cu) * cus)))), dim3(THREADS), 0, stream,
+                       (const uint64_t *)keys, alt, m, hi.n_tiles2, shift2, bits2, (const unsigned long long *)segtab.p,
+                       (unsigned long long *)nullptr, tickets.p + 1, d_fail, 0u, cur2.p, 1u, 64u, 0u);
+    std::swap(keys, alt);
+    DevArray<uint32_t> tc(m), n_distinct(EB_TABLE), dstart(EB_TABLE + 1);
+    SW_HIP(hipMemsetAsync(n_distinct.p, 0, n_distinct.bytes(), stream));
+    uint64_t *tk = alt;   // (the level-1 output is dead)
+    const size_t lds = (size_t)slots * 14;
+    static std::mutex &mu = *new std::mutex;   // (leaked on purpose, like the pool)
+    {
+        std::lock_guard<std::mutex> lock(mu);
+        SW_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k_eb_finish), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    }
+    hipLaunchKernelGGL(k_eb_finish, dim3(EB_TABLE), dim3(EB_THREADS), lds, stream, (const uint64_t *)keys, (const uint32_t *)start.p, slots,
+                       shift1, shift2, (1u << bits2) - 1u, bin_shift, (1u << bin_bits) - 1u, sentinel, tk, tc.p, n_distinct.p, flags.p);
+    hipLaunchKernelGGL(k_eb_scan, dim3(1), dim3(1024), 0, stream, (const uint32_t *)n_distinct.p, (const unsigned long long *)nullptr, 0u,
+                       dstart.p, (unsigned long long *)nullptr, (uint32_t *)nullptr, &info.p->n_runs);
+    hipLaunchKernelGGL(k_eb_compact, dim3(EB_TABLE), dim3(256), 0, stream, (const uint64_t *)tk, (const uint32_t *)tc.p,
+                       (const uint32_t *)start.p, (const uint32_t *)dstart.p, (const unsigned long long *)&info.p->n_sentinels, ukeys, ucnt,
+                       flags.p);
+    SW_HIP(hipGetLastError());
+    uint32_t hf = 0;
+    SW_HIP(hipMemcpyAsync(&hi, info.p, sizeof hi, hipMemcpyDeviceToHost, stream));
+    SW_HIP(hipMemcpyAsync(&hf, flags.p, 4, hipMemcpyDeviceToHost, stream));
+    SW_HIP(hipStreamSynchronize(stream));
+    if (hf & (EB_F_RANGE | EB_F_ORDER))
+        raise(SW_ERR_RUNTIME, "internal error: the edge buckets are out of order (%s)", hf & EB_F_RANGE ? "a key outside its bucket" : "run starts descend");
+    if (hf & EB_F_OVERFLOW) {
+        if (debug) fprintf(stderr, "[edge buckets] a sub-bucket holds more than %u distinct keys: radix passes instead\n", slots);
+        return 1;
+    }
+    *n_runs = hi.n_runs;
+    return 0;
 }
 
 // which shape a sort of `bits` key bits takes: 0 = 512 threads x 8 bits, 1 = 1024 x 9, 2 = 1024 x 8, 3 = 512 x 9, 4 = 256 x 8 (the last three: A/B)
