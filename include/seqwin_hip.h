@@ -401,6 +401,18 @@ int sw_radix_rank_mode(int *mode);
 int sw_order_guard_trips(uint64_t *node_sort, uint64_t *edge_sort);
 int sw_sort_pairs32(void *keys_dev, void *keys_alt_dev, void *vals_dev, void *vals_alt_dev, uint64_t n, uint64_t end_bit, void *stream,
                     int *sorted_in_alt, double *ms);
+/* The bucket route of the edge sort on its own (csrc/radix.hip: radix_edge_buckets, what a single-device build takes from 2^26 edge
+ * keys on): m DEVICE u64 keys below 2^key_bits, the value 2^key_bits - 1 being the sentinel of a record boundary; keys_dev /
+ * alt_dev are a double buffer of m keys each.  key_bits in [1, 62]; cap: most real keys a sub-bucket may hold (< 2^32); slots: size
+ * of the LDS table of a sub-bucket's distinct keys; hist_top_dev: the counts of the keys' top digit (u64[2^digit width], DEVICE) as
+ * the producer of the keys takes them, NULL: counted here.
+ * *done = 1: ukeys_dev[0, *n_runs) (u64, room for m) holds the distinct real keys in ascending order, ucnt_dev[0, *n_runs] (u32, room
+ *            for m + 1) the start of every run of equal keys among the sorted real keys and, last, the number of real keys.
+ * *done = 0: the routine declined (fewer than two digits, m = 0 or m >= 2^32 - 1, slots no power of two in [64, 8192], a sub-bucket
+ *            above cap real keys or slots distinct keys); nothing else is valid, *n_runs = 0.
+ * Either way *keys_in_alt tells which buffer holds the multiset of the input keys afterwards (in some order). */
+int sw_edge_buckets(void *keys_dev, void *alt_dev, uint64_t m, uint64_t key_bits, uint64_t cap, uint64_t slots, const void *hist_top_dev,
+                    void *ukeys_dev, void *ucnt_dev, uint64_t *n_runs, int *done, int *keys_in_alt, void *stream);
 
 /* ---- pairs form of the adjacency exchange (what dist.py uses whenever every slice marked its ranks) ---------------------
  * The weight of an edge is the number of its adjacency records minus the records that repeat the pair inside one

@@ -1884,6 +1884,38 @@ int sw_sort_pairs32(void *keys_dev, void *keys_alt_dev, void *vals_dev, void *va
     });
 }
 
+int sw_edge_buckets(void *keys_dev, void *alt_dev, uint64_t m, uint64_t key_bits, uint64_t cap, uint64_t slots, const void *hist_top_dev,
+                    void *ukeys_dev, void *ucnt_dev, uint64_t *n_runs, int *done, int *keys_in_alt, void *stream)
+{
+    return guarded([&] {
+        if (!n_runs || !done || !keys_in_alt) raise(SW_ERR_VALUE, "n_runs, done and keys_in_alt must not be NULL");
+        if (key_bits < 1 || key_bits > 62) raise(SW_ERR_VALUE, "key_bits must be in [1, 62] (two node ranks of less than 32 bits)");
+        if (cap >> 32) raise(SW_ERR_VALUE, "cap must be below 2^32");
+        if (m && (!keys_dev || !alt_dev || !ukeys_dev || !ucnt_dev)) raise(SW_ERR_VALUE, "keys, alt, ukeys and ucnt must not be NULL");
+        *n_runs = 0;
+        *done = 0;
+        *keys_in_alt = 0;
+        if (m == 0) return;   // (edges_from_pairs never sorts an empty set)
+        require_device();
+        StreamScope scope((hipStream_t)stream);
+        uint64_t *k = (uint64_t *)keys_dev, *a = (uint64_t *)alt_dev;
+        DevArray<uint32_t> fail(1);
+        SW_HIP(hipMemsetAsync(fail.p, 0, 4, (hipStream_t)stream));
+        uint32_t runs = 0;
+        const int declined = radix_edge_buckets(k, a, m, (unsigned)key_bits, (1ull << key_bits) - 1ull, (const unsigned long long *)hist_top_dev,
+                                                (uint32_t)cap, (uint32_t)std::min<uint64_t>(slots, 0xFFFFFFFFull), (uint64_t *)ukeys_dev,
+                                                (uint32_t *)ucnt_dev, &runs, (hipStream_t)stream, fail.p,
+                                                getenv("SEQWIN_AMD_DEBUG_EDGE_REPAIR") != nullptr);
+        uint32_t failed = 0;
+        SW_HIP(hipMemcpyAsync(&failed, fail.p, 4, hipMemcpyDeviceToHost, (hipStream_t)stream));
+        SW_HIP(hipStreamSynchronize((hipStream_t)stream));
+        check_sort_failed(failed);
+        *keys_in_alt = (k == (uint64_t *)alt_dev) ? 1 : 0;
+        *done = declined ? 0 : 1;
+        *n_runs = declined ? 0 : runs;
+    });
+}
+
 int sw_index_ranks_marked(const sw_index *ix, int *marked)
 {
     return guarded([&] { *marked = ix->ranks_marked ? 1 : 0; });

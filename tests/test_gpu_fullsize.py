@@ -75,17 +75,31 @@ def test_config1_full_size_equals_reference(tmp_path):
     assert v["weight_sum"] == int(ee["weight"].sum())
 
 
+_EDGE_BUCKETS_LOG = r"\[edge buckets\] \d+ keys, \d+ sentinels, digits \d+\+\d+\+\d+ of \d+ bits, largest sub-bucket (\d+) \(capacity (\d+), \d+ slots\)"
+
+
 @pytest.mark.parametrize("w", [200, 10])
-def test_config1_full_size_checksums_of_the_reference(w):
+def test_config1_full_size_checksums_of_the_reference(w, monkeypatch, capfd):
     """configs[1] at full size in the small-window regime too: 512 genomes at w = 10 are 4.5e8 occurrences, 6.6e7 nodes, 8.1e7 edges --
     the index stages dominate (54 ms), the compiled reference needs 183 s for it on the GPU box's host.  Counts and checksums were
     computed from the REFERENCE's arrays there (scripts/pin_fullsize_ref.py, every array also compared element for element;
-    tests/golden/bench_checksums_ref.json), with every other assembly a target."""
+    tests/golden/bench_checksums_ref.json), with every other assembly a target.
+    At w = 10 (4.5e8 edge keys, 6.7 per node) the edges take the bucket route of csrc/radix.hip by default and finish on it: the
+    log line of SEQWIN_AMD_DEBUG_EDGE_REPAIR says so."""
+    import re
     G, rpg, rl, anc, snp, _ = WORKLOADS["salmonella500"]
     gold, src = _full_size_golden(f"salmonella500/k21/w{w}")
     assert src == "reference"
+    monkeypatch.setenv("SEQWIN_AMD_DEBUG_EDGE_REPAIR", "1")
     b = Batch.synthetic(G, rpg, rl, n_ancestors=anc, snp_ppm=snp, seed=SEED)
+    capfd.readouterr()
     ix = b.build_index(21, w, np.arange(G) % 2 == 0)
+    err = capfd.readouterr().err
+    if w == 10:
+        line = re.search(_EDGE_BUCKETS_LOG, err)
+        assert line, err[-2000:]
+        assert "radix passes instead" not in err and "distinct keys" not in err, err[-2000:]
+        assert int(line.group(1)) <= int(line.group(2)), line.group(0)
     nk, nn, ne = ix.sizes()
     assert gold["counts"] == {"kmers": nk, "nodes": nn, "edges": ne}
     assert [f"{s:016x}" for s in ix.checksums()] == gold["checksums"]
@@ -519,17 +533,23 @@ def test_config4_share_through_the_sharded_path(k):
 
 
 @pytest.mark.parametrize("k", [15, 19, 31])
-def test_config4_slice(tmp_path, k):
+def test_config4_slice(tmp_path, k, monkeypatch, capfd):
     """BASELINE configs[4] (100 000 x 5 Mbp iid-random genomes over 8 GPUs, k in {15, 19, 31}): one GPU's share,
     12 500 genomes = 62.5 Gbp, every minimizer nearly its own node at k >= 19 (622 M nodes, 60-bit edge keys).
     Device-side structural self-check, the committed checksums, and the first 64 genomes of the same generator against
-    the compiled reference."""
+    the compiled reference.  At k >= 19 there are fewer than four edge keys per node: the edges keep the radix
+    passes, no [edge buckets] line."""
     G, rpg, rl, anc, snp, _ = WORKLOADS["random100k"]
     w = 200
+    monkeypatch.setenv("SEQWIN_AMD_DEBUG_EDGE_REPAIR", "1")
     b = Batch.synthetic(G, rpg, rl, n_ancestors=anc, snp_ppm=snp, seed=SEED)
     tar = np.arange(G) % 2 == 0
+    capfd.readouterr()
     ix = b.build_index(k, w, tar)
+    err = capfd.readouterr().err
     nk, nn, ne = ix.sizes()
+    if nk - 1 <= 4 * nn:
+        assert k >= 19 and "[edge buckets]" not in err, err[-2000:]
     t = ix.timings()
     assert t["total_bp"] == G * rpg * rl == 62_500_000_000
     assert 0.0097 < nk / t["total_bp"] < 0.0102
