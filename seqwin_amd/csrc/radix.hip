@@ -1441,7 +1441,7 @@ static_assert(EB_THREADS == EB_RADIX, "k_eb_finish: one bin per thread");
 enum : uint32_t { EB_F_OVERFLOW = 1u, EB_F_RANGE = 2u, EB_F_ORDER = 4u };
 struct EbInfo {   // device -> host after the counting sweep
     unsigned long long n_sentinels;
-    uint32_t n_tiles2, max_bucket, flags, n_runs;
+    uint32_t n_tiles2, max_bucket, flags, n_runs, n_live, pad;
 };
 
 // one workgroup of EB_RADIX threads: level-1 cursors from the digit counts, and the tile table of the level-2 sweeps
@@ -1510,22 +1510,25 @@ __global__ __launch_bounds__(1024) void k_eb_count(const uint64_t *__restrict__ 
 }
 
 // one workgroup: start[i] = sum of cnt[< i] over the EB_TABLE sub-buckets (start[EB_TABLE] = total), the largest count -- not
-// counting the *n_sent sentinels of sub-bucket sent_at -- and, for the level-2 pass, its cursors
+// counting the *n_sent sentinels of sub-bucket sent_at -- and, for the level-2 pass, its cursors and the list of the non-empty
+// sub-buckets, (id, start, count, 0) each, the highest id first (the sentinels' long one starts first): live[0, *n_live_out)
 __global__ __launch_bounds__(1024) void k_eb_scan(const uint32_t *__restrict__ cnt, const unsigned long long *__restrict__ n_sent,
                                                   uint32_t sent_at, uint32_t *__restrict__ start, unsigned long long *__restrict__ cursor,
-                                                  uint32_t *__restrict__ max_out, uint32_t *__restrict__ total_out)
+                                                  uint32_t *__restrict__ max_out, uint32_t *__restrict__ total_out,
+                                                  uint4 *__restrict__ live, uint32_t *__restrict__ n_live_out)
 {
     constexpr uint32_t PER4 = EB_TABLE / 1024 / 4;   // a thread's 256 consecutive counts as 64 16-byte loads, sixteen in flight
-    __shared__ uint32_t ws[16], wm[16];
+    __shared__ uint32_t ws[16], wm[16], wz[16];
     const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
     const uint32_t sent = n_sent ? (uint32_t)*n_sent : 0u;
     const uint4 *cnt4 = reinterpret_cast<const uint4 *>(cnt) + (size_t)tid * PER4;
-    uint32_t sum = 0, mx = 0;
+    uint32_t sum = 0, mx = 0, nz = 0;
 #pragma unroll 16
     for (uint32_t j = 0; j < PER4; ++j) {
         const uint4 c = cnt4[j];
         mx = max(max(max(mx, c.x), max(c.y, c.z)), c.w);
         sum += c.x + c.y + c.z + c.w;
+        nz += (c.x != 0) + (c.y != 0) + (c.z != 0) + (c.w != 0);
     }
     if (n_sent && sent_at / (4 * PER4) == tid) {   // (the largest count leaves the sentinels out)
         mx = 0;
@@ -1534,17 +1537,30 @@ __global__ __launch_bounds__(1024) void k_eb_scan(const uint32_t *__restrict__ c
             mx = max(mx, c - (i == sent_at ? min(c, sent) : 0u));
         }
     }
-    uint32_t incl = sum;
+    uint32_t incl = sum, inz = nz;
     for (uint32_t o = 1; o < 64; o <<= 1) {
-        const uint32_t up = __shfl_up(incl, o, 64);
-        if (lane >= o) incl += up;
+        const uint32_t up = __shfl_up(incl, o, 64), uz = __shfl_up(inz, o, 64);
+        if (lane >= o) {
+            incl += up;
+            inz += uz;
+        }
         mx = max(mx, __shfl_xor(mx, o, 64));
     }
-    if (lane == 63) ws[wave] = incl;
+    if (lane == 63) {
+        ws[wave] = incl;
+        wz[wave] = inz;
+    }
     if (lane == 0) wm[wave] = mx;
     __syncthreads();
-    uint32_t run = incl - sum;
-    for (uint32_t w = 0; w < wave; ++w) run += ws[w];
+    uint32_t run = incl - sum, below = inz - nz, n_live = 0;
+    for (uint32_t w = 0; w < 16; ++w) {
+        if (w < wave) {
+            run += ws[w];
+            below += wz[w];
+        }
+        n_live += wz[w];
+    }
+    uint32_t at = n_live - 1u - below;   // (the place of this thread's first non-empty sub-bucket; used only if it has one)
     uint4 *start4 = reinterpret_cast<uint4 *>(start) + (size_t)tid * PER4;
     ulonglong2 *cur2 = reinterpret_cast<ulonglong2 *>(cursor) + (size_t)tid * PER4 * 2;
 #pragma unroll 16
@@ -1556,99 +1572,172 @@ __global__ __launch_bounds__(1024) void k_eb_scan(const uint32_t *__restrict__ c
             cur2[2 * j] = make_ulonglong2(st.x, st.y);
             cur2[2 * j + 1] = make_ulonglong2(st.z, st.w);
         }
+        if (live) {
+            const uint32_t id = (tid * PER4 + j) * 4;
+            if (c.x) live[at--] = make_uint4(id, st.x, c.x, 0u);
+            if (c.y) live[at--] = make_uint4(id + 1, st.y, c.y, 0u);
+            if (c.z) live[at--] = make_uint4(id + 2, st.z, c.z, 0u);
+            if (c.w) live[at--] = make_uint4(id + 3, st.w, c.w, 0u);
+        }
         run = st.w + c.w;
     }
     if (tid == 1023) {
         start[EB_TABLE] = run;
         if (total_out) *total_out = run;
+        if (n_live_out) *n_live_out = n_live;
         uint32_t m = 0;
         for (uint32_t w = 0; w < 16; ++w) m = max(m, wm[w]);
         if (max_out) *max_out = m;
     }
 }
 
-// One sub-bucket per workgroup (from the last one down: the sentinels' is the longest).  Dynamic LDS: slots x (8 + 4 + 2) bytes.
-__global__ __launch_bounds__(EB_THREADS) void k_eb_finish(const uint64_t *__restrict__ in, const uint32_t *__restrict__ start, uint32_t slots,
+#ifdef SW_RS_STAMPS   // timing builds: thread 0 of every 16th workgroup writes the shader clock at its phase boundaries (16 words each)
+__device__ unsigned long long *g_eb_stamps = nullptr;
+constexpr uint32_t EB_ST_EVERY = 16, EB_ST_WORDS = 16;
+#define EB_STAMP(i) do { if (st) st[i] = clock64(); } while (0)
+#define EB_STAMP_ADD(i, since) do { if (st) { const unsigned long long t_ = clock64(); st[i] += t_ - (since); (since) = t_; } } while (0)
+#else
+#define EB_STAMP(i) do { } while (0)
+#define EB_STAMP_ADD(i, since) do { } while (0)
+#endif
+
+// One sub-bucket per workgroup, the non-empty ones only (live[]: id, start, count; from the last one down: the sentinels' is the
+// longest).  A slot of the table is, PACKED, ONE word (key bits below shift2) << cb | copies -- the bits above are the sub-bucket's
+// own and a count is below 2^cb, cb the bit length of the largest sub-bucket; shift2 + cb <= 63, so no word equals EB_EMPTY --
+// else a key and a count.  Dynamic LDS: slots x (8 + 2) or slots x (8 + 4 + 2) bytes.  The keys of the next step are loaded before
+// those of this one go in; a step's four keys per lane probe together, one compare-and-swap each per trip.
+template <bool PACKED>
+__global__ __launch_bounds__(EB_THREADS) void k_eb_finish(const uint64_t *__restrict__ in, const uint4 *__restrict__ live, uint32_t slots,
                                                           unsigned shift1, unsigned shift2, uint32_t mask2, unsigned bin_shift,
-                                                          uint32_t bin_mask, uint64_t sentinel,
+                                                          uint32_t bin_mask, unsigned cb, uint64_t sentinel,
                                                           uint64_t *__restrict__ tk, uint32_t *__restrict__ tc,
                                                           uint32_t *__restrict__ n_distinct, uint32_t *__restrict__ flags)
 {
     extern __shared__ __align__(16) unsigned char eb_lds[];
-    unsigned long long *hk = reinterpret_cast<unsigned long long *>(eb_lds);
-    uint32_t *hc = reinterpret_cast<uint32_t *>(hk + slots);
-    uint16_t *idx = reinterpret_cast<uint16_t *>(hc + slots);
+    unsigned long long *hk = reinterpret_cast<unsigned long long *>(eb_lds);   // PACKED: the words
+    uint32_t *hc = reinterpret_cast<uint32_t *>(hk + slots);                   // (not PACKED only)
+    uint16_t *idx = PACKED ? reinterpret_cast<uint16_t *>(hk + slots) : reinterpret_cast<uint16_t *>(hc + slots);
     __shared__ uint32_t bd[EB_RADIX + 1], bk[EB_RADIX], bcur[EB_RADIX], wsd[EB_THREADS / 64], wsk[EB_THREADS / 64];
     __shared__ uint32_t s_over;
-    const uint32_t b = EB_TABLE - 1u - blockIdx.x, tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
-    const uint32_t first = start[b], cnt = start[b + 1] - first;
-    if (cnt == 0) return;
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+#ifdef SW_RS_STAMPS
+    unsigned long long *st = g_eb_stamps && tid == 0 && blockIdx.x % EB_ST_EVERY == 0 ? g_eb_stamps + (size_t)(blockIdx.x / EB_ST_EVERY) * EB_ST_WORDS : nullptr;
+    unsigned long long st_t = 0;
+#endif
+    EB_STAMP(0);
+    const uint4 me = live[blockIdx.x];   // (one 16-byte load, the same for every lane, in flight while the table is cleared)
     const uint32_t mask = slots - 1u;
     for (uint32_t s = tid; s < slots; s += EB_THREADS) {
         hk[s] = EB_EMPTY;
-        hc[s] = 0;
+        if (!PACKED) hc[s] = 0;
     }
     bd[tid] = 0;
     bk[tid] = 0;
     if (tid == 0) s_over = 0;
+    const uint32_t b = me.x, first = me.y, cnt = me.z;
+    const uint64_t low_mask = (1ull << shift2) - 1ull, count_mask = (1ull << cb) - 1ull;
+    const uint64_t high = ((uint64_t)(b / EB_RADIX) << shift1) | ((uint64_t)(b % EB_RADIX) << shift2);   // the key bits a sub-bucket shares
+    uint64_t nxt[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const uint32_t j = i * EB_THREADS + tid;
+        nxt[i] = j < cnt ? in[(uint64_t)first + j] : sentinel;
+    }
+    EB_STAMP(1);
     __syncthreads();
+    EB_STAMP(2);
+#ifdef SW_RS_STAMPS
+    if (st) st_t = clock64();
+#endif
     uint32_t bad = 0;
     for (uint32_t j0 = 0; j0 < cnt; j0 += 4 * EB_THREADS) {
         if (*(volatile uint32_t *)&s_over) break;
         uint64_t key[4];
 #pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const uint32_t j = j0 + i * EB_THREADS + tid;
-            key[i] = j < cnt ? in[(uint64_t)first + j] : sentinel;
+        for (int i = 0; i < 4; ++i) key[i] = nxt[i];
+        if (j0 + 4 * EB_THREADS < cnt) {   // the next step's loads, before this step's keys go in
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const uint32_t j = j0 + 4 * EB_THREADS + i * EB_THREADS + tid;
+                nxt[i] = j < cnt ? in[(uint64_t)first + j] : sentinel;
+            }
         }
+        // what each of the four keys does, decided before any of them probes: cp = copies to add (0: nothing to do), h = slot, w = word
+        uint32_t cp[4], h[4];
+        unsigned long long w[4];
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
-            uint64_t k = key[i];
-            bool live = k != sentinel;
-            if (live && ((uint32_t)(k >> shift1) * EB_RADIX + ((uint32_t)(k >> shift2) & mask2)) != b) {
+            const uint64_t k = key[i];
+            bool alive = k != sentinel;
+            if (alive && ((uint32_t)(k >> shift1) * EB_RADIX + ((uint32_t)(k >> shift2) & mask2)) != b) {
                 bad = 1;
-                live = false;
+                alive = false;
             }
             // the copies of the wave's first key go in as one (a hub node's pair fills whole waves)
             uint32_t copies = 1;
-            const uint64_t any = __ballot(live);
+            const uint64_t any = __ballot(alive);
             if (any) {
                 const int src = __ffsll((long long)any) - 1;
                 const uint64_t k0 = (uint64_t)__shfl((unsigned long long)k, src, 64);
-                const uint64_t same = __ballot(live && k == k0);
-                if (live && k == k0) {
+                const uint64_t same = __ballot(alive && k == k0);
+                if (alive && k == k0) {
                     copies = (uint32_t)__popcll(same);
-                    live = (int)lane == src;
+                    alive = (int)lane == src;
                 }
             }
-            if (!live) continue;
-            uint32_t h = (uint32_t)((k * 0x9E3779B97F4A7C15ull) >> 40) & mask, probes = 0;
-            for (; probes < slots; ++probes) {
-                const unsigned long long old = atomicCAS(&hk[h], EB_EMPTY, (unsigned long long)k);
-                if (old == EB_EMPTY || old == k) {
-                    atomicAdd(&hc[h], copies);
-                    break;
-                }
-                h = (h + 1u) & mask;
-            }
-            if (probes == slots) s_over = 1;
+            cp[i] = alive ? copies : 0u;
+            h[i] = (uint32_t)((k * 0x9E3779B97F4A7C15ull) >> 40) & mask;
+            w[i] = PACKED ? ((k & low_mask) << cb) | copies : (unsigned long long)k;
         }
+        EB_STAMP_ADD(3, st_t);
+        // one probe loop for the four: a key leaves it when it is placed.  Equal keys of a lane or a wave may meet at one empty slot in
+        // one trip: the atomics take them one after the other, and the later one finds the key there.
+        for (uint32_t probes = 0; cp[0] | cp[1] | cp[2] | cp[3]; ++probes) {
+            if (probes == slots) {   // (every slot seen, all taken by other keys)
+                s_over = 1;
+                break;
+            }
+            unsigned long long old[4];
+#pragma unroll
+            for (int i = 0; i < 4; ++i)
+                if (cp[i]) old[i] = atomicCAS(&hk[h[i]], EB_EMPTY, w[i]);
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                if (!cp[i]) continue;
+                if (PACKED) {
+                    if (old[i] == EB_EMPTY) cp[i] = 0;
+                    else if ((old[i] >> cb) == (w[i] >> cb)) {
+                        atomicAdd(&hk[h[i]], (unsigned long long)cp[i]);
+                        cp[i] = 0;
+                    } else h[i] = (h[i] + 1u) & mask;
+                } else {
+                    if (old[i] == EB_EMPTY || old[i] == w[i]) {
+                        atomicAdd(&hc[h[i]], cp[i]);
+                        cp[i] = 0;
+                    } else h[i] = (h[i] + 1u) & mask;
+                }
+            }
+        }
+        EB_STAMP_ADD(4, st_t);
     }
     if (bad) atomicOr(flags, EB_F_RANGE);
     __syncthreads();
+    EB_STAMP(5);
     if (s_over) {   // more distinct keys than slots: the caller sorts the untouched multiset by radix passes
         if (tid == 0) atomicOr(flags, EB_F_OVERFLOW);
         return;
     }
-    // distinct keys and copies per bin
+    // distinct keys and copies per bin (PACKED: the bins are bits of the word, cb higher)
+    const unsigned wbin_shift = PACKED ? bin_shift + cb : bin_shift;
     for (uint32_t s = tid; s < slots; s += EB_THREADS) {
         const uint64_t k = hk[s];
         if (k == EB_EMPTY) continue;
-        const uint32_t bin = (uint32_t)(k >> bin_shift) & bin_mask;
+        const uint32_t bin = (uint32_t)(k >> wbin_shift) & bin_mask;
         atomicAdd(&bd[bin], 1u);
-        atomicAdd(&bk[bin], hc[s]);
+        atomicAdd(&bk[bin], PACKED ? (uint32_t)(k & count_mask) : hc[s]);
     }
     __syncthreads();
+    EB_STAMP(6);
     {   // exclusive scans over the EB_RADIX bins (one bin per thread)
         const uint32_t d = bd[tid], c = bk[tid];
         uint32_t id = d, ic = c;
@@ -1665,9 +1754,9 @@ __global__ __launch_bounds__(EB_THREADS) void k_eb_finish(const uint64_t *__rest
         }
         __syncthreads();
         uint32_t pd = id - d, pc = ic - c;
-        for (uint32_t w = 0; w < wave; ++w) {
-            pd += wsd[w];
-            pc += wsk[w];
+        for (uint32_t w2 = 0; w2 < wave; ++w2) {
+            pd += wsd[w2];
+            pc += wsk[w2];
         }
         bd[tid] = pd;
         bcur[tid] = pd;
@@ -1675,47 +1764,74 @@ __global__ __launch_bounds__(EB_THREADS) void k_eb_finish(const uint64_t *__rest
         if (tid == EB_THREADS - 1) bd[EB_RADIX] = pd + d;
     }
     __syncthreads();
+    EB_STAMP(7);
     for (uint32_t s = tid; s < slots; s += EB_THREADS) {
         const uint64_t k = hk[s];
         if (k == EB_EMPTY) continue;
-        idx[atomicAdd(&bcur[(uint32_t)(k >> bin_shift) & bin_mask], 1u)] = (uint16_t)s;
+        idx[atomicAdd(&bcur[(uint32_t)(k >> wbin_shift) & bin_mask], 1u)] = (uint16_t)s;
     }
     __syncthreads();
+    EB_STAMP(8);
     const uint32_t n_dist = bd[EB_RADIX];
     if (tid == 0) n_distinct[b] = n_dist;
     for (uint32_t j = tid; j < n_dist; j += EB_THREADS) {
         const uint32_t s = idx[j];
-        const uint64_t k = hk[s];
-        const uint32_t bin = (uint32_t)(k >> bin_shift) & bin_mask, lo = bd[bin], hi = bd[bin + 1];
+        const uint64_t k = hk[s];   // (PACKED: words order like their keys as long as the keys differ)
+        const uint32_t bin = (uint32_t)(k >> wbin_shift) & bin_mask, lo = bd[bin], hi = bd[bin + 1];
         uint32_t less = 0, copies_less = 0;
-        for (uint32_t i = lo; i < hi; ++i) {
-            const uint32_t s2 = idx[i];
-            if (hk[s2] < k) {
-                ++less;
-                copies_less += hc[s2];
+        // four members of the bin per trip, their reads independent of each other (a bin is one node's pairs: a hub's bin is long, and
+        // a read per member and trip left the wave waiting on one LDS round trip after the other); a place past the end reads the key itself
+        for (uint32_t i = lo; i < hi; i += 4) {
+            uint32_t s2[4];
+            unsigned long long k2[4];
+            uint32_t c2[4];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) s2[u] = i + u < hi ? idx[i + u] : s;
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                k2[u] = hk[s2[u]];
+                c2[u] = PACKED ? 0u : hc[s2[u]];
+            }
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                if (PACKED ? (k2[u] >> cb) < (k >> cb) : k2[u] < k) {
+                    ++less;
+                    copies_less += PACKED ? (uint32_t)(k2[u] & count_mask) : c2[u];
+                }
             }
         }
-        tk[(uint64_t)first + lo + less] = k;
+        tk[(uint64_t)first + lo + less] = PACKED ? high | (k >> cb) : k;
         tc[(uint64_t)first + lo + less] = first + bk[bin] + copies_less;
     }
+#ifdef SW_RS_STAMPS
+    if (st) {
+        st[9] = clock64();
+        st[10] = cnt;
+        st[11] = n_dist;
+    }
+#endif
 }
 
 // distinct keys and run starts from the buckets' own ranges to their run numbers; the order check where the data is in hand
 __global__ __launch_bounds__(256) void k_eb_compact(const uint64_t *__restrict__ tk, const uint32_t *__restrict__ tc,
-                                                    const uint32_t *__restrict__ start, const uint32_t *__restrict__ dstart,
+                                                    const uint4 *__restrict__ live, uint32_t n_live, const uint32_t *__restrict__ start,
+                                                    const uint32_t *__restrict__ dstart,
                                                     const unsigned long long *__restrict__ n_sentinels, uint64_t *__restrict__ ukeys,
                                                     uint32_t *__restrict__ ucnt, uint32_t *__restrict__ flags)
 {
-    const uint32_t b = blockIdx.x, d0 = dstart[b], n = dstart[b + 1] - d0;
-    if (b == EB_TABLE - 1u && threadIdx.x == 0) ucnt[dstart[EB_TABLE]] = start[EB_TABLE] - (uint32_t)*n_sentinels;
+    if (blockIdx.x == 0 && threadIdx.x == 0) ucnt[dstart[EB_TABLE]] = start[EB_TABLE] - (uint32_t)*n_sentinels;
+    if (blockIdx.x >= n_live) return;
+    const uint4 me = live[blockIdx.x];
+    const uint32_t b = me.x, d0 = dstart[b], n = dstart[b + 1] - d0;
     if (n == 0) return;
-    const uint64_t first = start[b];
+    const uint64_t first = me.y;
+    const uint32_t end = me.y + me.z;
     uint32_t bad = 0;
     for (uint32_t j = threadIdx.x; j < n; j += 256) {
         const uint64_t k = tk[first + j];
         const uint32_t c = tc[first + j];
         if (j + 1 < n && (tk[first + j + 1] <= k || tc[first + j + 1] <= c)) bad = 1;
-        if (c < first || c >= start[b + 1]) bad = 1;
+        if (c < first || c >= end) bad = 1;
         ukeys[d0 + j] = k;
         ucnt[d0 + j] = c;
     }
@@ -1750,6 +1866,7 @@ int radix_edge_buckets(uint64_t *&keys, uint64_t *&alt, uint64_t m, unsigned key
 
     DevArray<unsigned long long> h1(EB_RADIX), cur1((size_t)EB_RADIX * RS_CURSOR_STRIDE), cur2(EB_TABLE), segtab(max_tiles2);
     DevArray<uint32_t> table(EB_TABLE), start(EB_TABLE + 1), tickets(2), flags(1);
+    DevArray<uint4> live(EB_TABLE);
     DevArray<EbInfo> info(1);
     SW_HIP(hipMemsetAsync(h1.p, 0, h1.bytes(), stream));
     SW_HIP(hipMemsetAsync(table.p, 0, table.bytes(), stream));
@@ -1772,16 +1889,37 @@ int radix_edge_buckets(uint64_t *&keys, uint64_t *&alt, uint64_t m, unsigned key
                        sentinel, table.p, info.p);
     const uint32_t sent_at = (uint32_t)(sentinel >> shift1) * EB_RADIX + ((uint32_t)(sentinel >> shift2) & ((1u << bits2) - 1u));
     hipLaunchKernelGGL(k_eb_scan, dim3(1), dim3(1024), 0, stream, (const uint32_t *)table.p, (const unsigned long long *)&info.p->n_sentinels,
-                       sent_at, start.p, cur2.p, &info.p->max_bucket, (uint32_t *)nullptr);
+                       sent_at, start.p, cur2.p, &info.p->max_bucket, (uint32_t *)nullptr, live.p, &info.p->n_live);
     SW_HIP(hipGetLastError());
     EbInfo hi;
     SW_HIP(hipMemcpyAsync(&hi, info.p, sizeof hi, hipMemcpyDeviceToHost, stream));
     SW_HIP(hipStreamSynchronize(stream));
-    if (debug)
-        fprintf(stderr, "[edge buckets] %llu keys, %llu sentinels, digits %u+%u+%u of %u bits, largest sub-bucket %u (capacity %u, %u slots)%s\n",
+    // the finish kernel's slots: one packed word where key and count fit one that can never read as empty (k_eb_finish), else key + count
+    unsigned cb = 1;
+    while (cb < 32 && (hi.max_bucket >> cb)) ++cb;   // (a count is at most the largest sub-bucket)
+    const bool eligible = shift2 + cb <= 63;
+    bool packed = eligible;
+    if (const char *e = SW_TEST_GETENV("SEQWIN_AMD_EDGE_FINISH")) packed = !strcmp(e, "packed");   // tests: packed | plain
+    const bool refused = packed && !eligible;
+    const size_t lds = (size_t)slots * (packed ? 10 : 14);
+    auto finish = packed ? k_eb_finish<true> : k_eb_finish<false>;
+    static std::mutex &mu = *new std::mutex;   // (leaked on purpose, like the pool)
+    static int lds_set[2] = {0, 0};             // the attribute belongs to the process: it only ever grows
+    {
+        std::lock_guard<std::mutex> lock(mu);
+        lds_set[packed] = std::max(lds_set[packed], (int)lds);
+        SW_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(finish), hipFuncAttributeMaxDynamicSharedMemorySize, lds_set[packed]));
+    }
+    if (debug) {
+        int resident = 0;
+        SW_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&resident, finish, EB_THREADS, lds));
+        fprintf(stderr, "[edge buckets] %llu keys, %llu sentinels, digits %u+%u+%u of %u bits, largest sub-bucket %u (capacity %u, %u slots)%s; "
+                        "%u live sub-buckets, %s slots%s, %d workgroups per CU\n",
                 (unsigned long long)m, hi.n_sentinels, bits1, bits2, bin_bits, key_bits, hi.max_bucket, cap, slots,
-                hi.max_bucket > cap ? ": radix passes instead" : "");
-    if (hi.max_bucket > cap) return 1;   // (the keys are the level-1 output: the same multiset)
+                hi.max_bucket > cap ? ": radix passes instead" : "", hi.n_live, packed ? "packed" : "plain",
+                refused ? " do not fit: radix passes instead" : "", resident);
+    }
+    if (hi.max_bucket > cap || refused) return 1;   // (the keys are the level-1 output: the same multiset)
     auto pass2 = ballot_forced() ? k_rs_pass_p<THREADS, BITS, 0, true> : k_rs_pass_p<THREADS, BITS, 1, true>;
     hipLaunchKernelGGL(pass2, dim3(std::max(1u, std::min(hi.n_tiles2, (uint32_t)(std::max(1, per_cu) * cus)))), dim3(THREADS), 0, stream,
                        (const uint64_t *)keys, alt, m, hi.n_tiles2, shift2, bits2, (const unsigned long long *)segtab.p,
@@ -1790,19 +1928,53 @@ int radix_edge_buckets(uint64_t *&keys, uint64_t *&alt, uint64_t m, unsigned key
     DevArray<uint32_t> tc(m), n_distinct(EB_TABLE), dstart(EB_TABLE + 1);
     SW_HIP(hipMemsetAsync(n_distinct.p, 0, n_distinct.bytes(), stream));
     uint64_t *tk = alt;   // (the level-1 output is dead)
-    const size_t lds = (size_t)slots * 14;
-    static std::mutex &mu = *new std::mutex;   // (leaked on purpose, like the pool)
-    {
-        std::lock_guard<std::mutex> lock(mu);
-        SW_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k_eb_finish), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+#ifdef SW_RS_STAMPS
+    DevArray<unsigned long long> stamps;
+    const size_t n_st = (size_t)(hi.n_live / EB_ST_EVERY + 1) * EB_ST_WORDS;
+    if (getenv("SEQWIN_AMD_STAMPS")) {
+        stamps.alloc(n_st);
+        SW_HIP(hipMemsetAsync(stamps.p, 0, stamps.bytes(), stream));
+        unsigned long long *ptr = stamps.p;
+        SW_HIP(hipMemcpyToSymbolAsync(HIP_SYMBOL(g_eb_stamps), &ptr, sizeof ptr, 0, hipMemcpyHostToDevice, stream));
     }
-    hipLaunchKernelGGL(k_eb_finish, dim3(EB_TABLE), dim3(EB_THREADS), lds, stream, (const uint64_t *)keys, (const uint32_t *)start.p, slots,
-                       shift1, shift2, (1u << bits2) - 1u, bin_shift, (1u << bin_bits) - 1u, sentinel, tk, tc.p, n_distinct.p, flags.p);
+#endif
+    if (hi.n_live)
+        hipLaunchKernelGGL(finish, dim3(hi.n_live), dim3(EB_THREADS), lds, stream, (const uint64_t *)keys, (const uint4 *)live.p, slots, shift1,
+                           shift2, (1u << bits2) - 1u, bin_shift, (1u << bin_bits) - 1u, cb, sentinel, tk, tc.p, n_distinct.p, flags.p);
+#ifdef SW_RS_STAMPS
+    if (stamps.p) {   // mean clocks per phase over the sampled workgroups of a mean sub-bucket (three steps of keys)
+        std::vector<unsigned long long> hs(n_st);
+        SW_HIP(hipStreamSynchronize(stream));
+        SW_HIP(hipMemcpy(hs.data(), stamps.p, stamps.bytes(), hipMemcpyDeviceToHost));
+        unsigned long long *none = nullptr;
+        SW_HIP(hipMemcpyToSymbol(HIP_SYMBOL(g_eb_stamps), &none, sizeof none));
+        double acc[10] = {0}, keys_sum = 0, dist_sum = 0;
+        size_t cnt = 0;
+        for (size_t t = 0; t + EB_ST_WORDS <= n_st; t += EB_ST_WORDS) {
+            if (!hs[t] || !hs[t + 9] || hs[t + 10] <= 2 * 4 * EB_THREADS || hs[t + 10] > 3 * 4 * EB_THREADS) continue;
+            acc[1] += (double)(hs[t + 1] - hs[t]);       // first instruction -> first keys requested
+            acc[2] += (double)(hs[t + 2] - hs[t + 1]);   // table cleared, barrier (waits for the first keys)
+            acc[3] += (double)hs[t + 3];                 // merge decisions of all steps (with what they wait for the keys)
+            acc[4] += (double)hs[t + 4];                 // probe loops of all steps
+            acc[5] += (double)(hs[t + 5] - hs[t + 2]) - (double)hs[t + 3] - (double)hs[t + 4];   // barrier behind the key loop
+            for (int i = 6; i <= 9; ++i) acc[i] += (double)(hs[t + i] - hs[t + i - 1]);
+            keys_sum += (double)hs[t + 10];
+            dist_sum += (double)hs[t + 11];
+            ++cnt;
+        }
+        static const char *nm[] = {"", "entry+list", "init+barrier", "merge(+key wait)", "probes", "loop barrier", "bin count", "scan", "scatter", "rank+store"};
+        fprintf(stderr, "[eb stamps] %s slots, %zu workgroups of 3 steps sampled (mean %.0f keys, %.0f distinct); mean clocks:", packed ? "packed" : "plain",
+                cnt, cnt ? keys_sum / cnt : 0.0, cnt ? dist_sum / cnt : 0.0);
+        double sum = 0;
+        for (int i = 1; i <= 9; ++i) { fprintf(stderr, " %s=%.0f", nm[i], cnt ? acc[i] / cnt : 0.0); sum += cnt ? acc[i] / cnt : 0.0; }
+        fprintf(stderr, " | workgroup %.0f\n", sum);
+    }
+#endif
     hipLaunchKernelGGL(k_eb_scan, dim3(1), dim3(1024), 0, stream, (const uint32_t *)n_distinct.p, (const unsigned long long *)nullptr, 0u,
-                       dstart.p, (unsigned long long *)nullptr, (uint32_t *)nullptr, &info.p->n_runs);
-    hipLaunchKernelGGL(k_eb_compact, dim3(EB_TABLE), dim3(256), 0, stream, (const uint64_t *)tk, (const uint32_t *)tc.p,
-                       (const uint32_t *)start.p, (const uint32_t *)dstart.p, (const unsigned long long *)&info.p->n_sentinels, ukeys, ucnt,
-                       flags.p);
+                       dstart.p, (unsigned long long *)nullptr, (uint32_t *)nullptr, &info.p->n_runs, (uint4 *)nullptr, (uint32_t *)nullptr);
+    hipLaunchKernelGGL(k_eb_compact, dim3(std::max(1u, hi.n_live)), dim3(256), 0, stream, (const uint64_t *)tk, (const uint32_t *)tc.p,
+                       (const uint4 *)live.p, hi.n_live, (const uint32_t *)start.p, (const uint32_t *)dstart.p,
+                       (const unsigned long long *)&info.p->n_sentinels, ukeys, ucnt, flags.p);
     SW_HIP(hipGetLastError());
     uint32_t hf = 0;
     SW_HIP(hipMemcpyAsync(&hi, info.p, sizeof hi, hipMemcpyDeviceToHost, stream));
