@@ -313,6 +313,57 @@ void sw_subgraphs_free(sw_subgraphs *sg);
  * (filter.cpp:139-201) as kmers.py:113-116 calls it after the walk. */
 int sw_index_filter_kmers_sg(const sw_index *ix, const sw_index *nodes_from, const sw_subgraphs *sg, sw_index **out);
 
+/* ---- markers._get_cks' per-subgraph work (src/seqwin/markers.py:95-300, 356-426) on the device (csrc/markers.hip) ----------
+ * For every subgraph: its location in every assembly (ConnectedKmers.__get_loc, markers.py:192-254) and its representative
+ * k-mer ordering with the row that carries it (__get_rep_order, markers.py:256-299; `rep`, markers.py:160).
+ * Items of a (subgraph, assembly) pair: the occurrences of the subgraph's nodes in the assembly's records, by (record_idx, pos).
+ * A run of consecutive minimizers ends at a change of record and where 2 * (pos - previous pos) > 3 * windowsize
+ * (pos.diff() > 1.5 * windowsize, markers.py:217, in integers).  A row describes the largest run of its assembly, the earliest
+ * one on ties (idxmax, markers.py:240-244); assemblies without an item have no row; rows ascend by assembly.  Targets are the
+ * assemblies below n_tar.  record_idx is local to the assembly, stop = last pos + kmerlen in uint32 as the reference's column. */
+typedef struct sw_marker_row {
+    uint32_t assembly_idx;
+    uint32_t record_idx;
+    uint32_t start;
+    uint32_t stop;
+    uint32_t n_kmers;
+    uint32_t n_repeats; /* runs of the subgraph in this assembly */
+} sw_marker_row;
+#define SW_MARKER_SINGLE 1u    /* the representative ordering has one k-mer (markers.py:294-295) */
+#define SW_MARKER_DUP 2u       /* a hash occurs twice in it (markers.py:296-297) */
+#define SW_MARKER_NO_TARGET 4u /* no target assembly holds the subgraph: the reference raises ValueError (max of an empty sequence, markers.py:283) */
+typedef struct sw_marker_rep {
+    sw_marker_row row; /* the lowest-assembly row whose ordering is the representative one (markers.py:160) */
+    uint32_t n_rep;    /* target rows with the representative's canonical ordering (markers.py:299); 0 with SW_MARKER_NO_TARGET */
+    uint32_t flags;
+} sw_marker_rep;
+typedef struct sw_markers sw_markers; /* opaque device-resident result */
+/* The resident route: kept = the index of sw_index_filter_kmers_sg, sg = the walk's result; subgraphs in commit order.
+ * record_offsets[n_assemblies + 1] (host) must be non-decreasing and cover the records of the index, n_tar <= n_assemblies,
+ * windowsize >= 1 (SW_ERR_VALUE otherwise).  keep_rows != 0 keeps the table of all rows for sw_markers_export_rows (the
+ * reference drops `loc`, markers.py:174-180). */
+int sw_index_marker_locs(const sw_index *kept, const sw_subgraphs *sg, const uint32_t *record_offsets, uint64_t n_assemblies,
+                         uint64_t n_tar, uint64_t kmerlen, uint64_t windowsize, int keep_rows, sw_markers **out);
+/* The same on host arrays (what _get_create_ck_args hands to _create_ck, markers.py:389-425): nodes strictly ascending by hash
+ * with [start, stop) into kmers, the occurrences of a node strictly ascending by (record_idx, pos); subgraph s holds the nodes
+ * sg_nodes[sg_offsets[s] .. sg_offsets[s + 1]) (indices into nodes). */
+int sw_marker_locs_from_arrays(const sw_kmer *kmers, uint64_t n_kmers, const sw_node *nodes, uint64_t n_nodes,
+                               const uint64_t *sg_offsets, const uint64_t *sg_nodes, uint64_t n_sg, const uint32_t *record_offsets,
+                               uint64_t n_assemblies, uint64_t n_tar, uint64_t kmerlen, uint64_t windowsize, int keep_rows,
+                               sw_markers **out);
+/* Subgraphs, hashes of all representative orderings, rows, hashes of all rows' orderings (0 unless the rows were kept). */
+int sw_markers_sizes(const sw_markers *m, uint64_t *n_sg, uint64_t *n_rep_kmers, uint64_t *n_rows, uint64_t *n_row_kmers);
+/* D2H copies (any pointer may be NULL): reps[n_sg], rep_offsets[n_sg + 1] into rep_hashes[n_rep_kmers]. */
+int sw_markers_export(const sw_markers *m, sw_marker_rep *reps, uint64_t *rep_offsets, uint64_t *rep_hashes);
+/* The rows of subgraph s are rows[row_offsets[s] .. row_offsets[s + 1]); row r's ordering is
+ * row_hashes[kmer_offsets[r] .. kmer_offsets[r + 1]).  SW_ERR_VALUE unless the call kept the rows. */
+int sw_markers_export_rows(const sw_markers *m, uint64_t *row_offsets, sw_marker_row *rows, uint64_t *kmer_offsets,
+                           uint64_t *row_hashes);
+/* counters[4] = { non-empty pairs (rows), pairs sorted in the HBM scratch, items of the largest pair, subgraphs voted in the HBM
+ * scratch }; ms[4] = { counts + offsets, rows, vote, results } (HIP events). */
+int sw_markers_stats(const sw_markers *m, uint64_t *counters, double *ms);
+void sw_markers_free(sw_markers *m);
+
 /* ---- multi-GPU merge (one process per GPU; the exchange itself is done by the host side with
  *      torch.distributed / RCCL on the device buffers below).  Together these replace
  *      merge_thread_graphs (cpp/src/seqwin/build_internals.cpp:295-392) across GPUs. -------------- */

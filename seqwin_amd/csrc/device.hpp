@@ -400,6 +400,9 @@ void slice_edges_pairs(sw_index &ix, uint64_t *d_keys, uint64_t m, const uint64_
                        unsigned hi_bits, uint64_t lo_base, unsigned ab, const uint64_t *d_rank_hash, const uint64_t *node_base,
                        uint32_t n_owners, uint64_t pad, hipStream_t stream);
 void index_node_hashes(const sw_index &ix, uint64_t *d_out, hipStream_t stream);
+// subgraph.hip: what markers.hip reads of a sw_subgraphs -- its device, sizes and the device CSR (offsets[n_sg + 1], hashes[n_out],
+// commit order, hashes ascending inside a subgraph)
+void subgraphs_csr(const sw_subgraphs *sg, int *device, uint64_t *n_sg, uint64_t *n_out, const uint64_t **offsets, const uint64_t **hashes);
 // rank -> hash by request instead of the job-wide table (slices whose edges hold ranks): the distinct endpoint ranks of the
 // slice's edges as owner-local ranks grouped by node owner (counts_host[n_owners]); lookups at the node owner; the replies,
 // in the order of the requests, put into the edges

@@ -728,6 +728,16 @@ void run_subgraphs(const sw_index &f, double th, uint64_t min_nodes, uint64_t ma
 }
 
 }  // namespace
+
+void subgraphs_csr(const sw_subgraphs *sg, int *device, uint64_t *n_sg, uint64_t *n_out, const uint64_t **offsets, const uint64_t **hashes)
+{
+    *device = sg->device;
+    *n_sg = sg->n_sg;
+    *n_out = sg->n_out;
+    *offsets = sg->offsets.p;
+    *hashes = sg->hashes.p;
+}
+
 }  // namespace sw
 
 using namespace sw;

@@ -213,6 +213,20 @@ class Index:
         sg.order = np.asarray(order, np.int64)
         return sg
 
+    def marker_locs(self, subgraphs: "Subgraphs", record_offsets, n_tar: int, kmerlen: int, windowsize: int,
+                    keep_rows: bool = False) -> "Markers":
+        """markers._get_cks' per-subgraph work (src/seqwin/markers.py:192-299) on the device (csrc/markers.hip): where every
+        subgraph lies in every assembly and its representative k-mer ordering.  ``self`` is the kept index
+        (``ix.filter_kmers(f, subgraphs)``).  Raises ValueError, as the reference does, when a subgraph lies in no target."""
+        ro = np.ascontiguousarray(record_offsets, np.uint32)
+        if ro.ndim != 1 or len(ro) < 1:
+            raise ValueError("record_offsets needs one entry per assembly and one more")
+        h = c_vp()
+        check(lib.sw_index_marker_locs(self._h, subgraphs._h, _ptr(ro), c_u64(max(len(ro) - 1, 0)), c_u64(int(n_tar)),
+                                       c_u64(int(kmerlen)), c_u64(int(windowsize)), ctypes.c_int(1 if keep_rows else 0),
+                                       ctypes.byref(h)))
+        return Markers(h, subgraphs.order)
+
     def save_npz(self, path, record_offsets) -> None:
         """Write ``graph.npz`` exactly as ``--save-graph`` does (src/seqwin/core.py:134-145)."""
         kmers, nodes, edges = self.export()
@@ -320,6 +334,112 @@ class Subgraphs:
     def close(self) -> None:
         if self._h:
             lib.sw_subgraphs_free(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+MARKER_ROW_DTYPE = np.dtype([("assembly_idx", "<u4"), ("record_idx", "<u4"), ("start", "<u4"), ("stop", "<u4"), ("n_kmers", "<u4"),
+                             ("n_repeats", "<u4")])
+MARKER_REP_DTYPE = np.dtype(MARKER_ROW_DTYPE.descr + [("n_rep", "<u4"), ("flags", "<u4")])
+MARKER_SINGLE, MARKER_DUP, MARKER_NO_TARGET = 1, 2, 4
+
+
+class Markers:
+    """Location and representative of every subgraph (:meth:`Index.marker_locs`), resident on the device.
+
+    The device keeps the subgraphs in commit order; every table handed out here is in the final order (``Subgraphs.order``, as
+    ``Subgraphs.csr`` applies it).  ``len`` of a row is ``stop - start`` in uint32, as the reference's column."""
+
+    def __init__(self, handle: c_vp, order=None):
+        self._h = handle
+        n_sg = self.sizes()[0]
+        self.order = np.arange(n_sg, dtype=np.int64) if order is None else np.asarray(order, np.int64)
+        if len(self.order) != n_sg:
+            self.close()
+            raise ValueError(f"the order has {len(self.order)} entries for {n_sg} subgraphs")
+        reps = self._reps_raw()[0]
+        bad = np.flatnonzero(reps["flags"][self.order] & MARKER_NO_TARGET)
+        if len(bad):
+            self.close()
+            raise ValueError(f"subgraph {int(bad[0])} lies in no target assembly (max() of an empty sequence in the reference)")
+
+    @classmethod
+    def from_arrays(cls, kmers, nodes, sg_offsets, sg_nodes, record_offsets, n_tar: int, kmerlen: int, windowsize: int,
+                    keep_rows: bool = False, order=None) -> "Markers":
+        """The direct route on host arrays: nodes ascending by hash with [start, stop) into kmers, subgraphs as CSR of node
+        indices."""
+        kmers = np.ascontiguousarray(kmers, KMER_DTYPE)
+        nodes = np.ascontiguousarray(nodes, NODE_DTYPE)
+        so = np.ascontiguousarray(sg_offsets, np.uint64)
+        sn = np.ascontiguousarray(sg_nodes, np.uint64)
+        ro = np.ascontiguousarray(record_offsets, np.uint32)
+        if len(so) < 1 or len(ro) < 1 or int(so[-1]) != len(sn):
+            raise ValueError("sg_offsets / record_offsets need at least one entry and sg_offsets[-1] == len(sg_nodes)")
+        h = c_vp()
+        check(lib.sw_marker_locs_from_arrays(_ptr(kmers), c_u64(len(kmers)), _ptr(nodes), c_u64(len(nodes)), _ptr(so), _ptr(sn),
+                                             c_u64(len(so) - 1), _ptr(ro), c_u64(len(ro) - 1), c_u64(int(n_tar)), c_u64(int(kmerlen)),
+                                             c_u64(int(windowsize)), ctypes.c_int(1 if keep_rows else 0), ctypes.byref(h)))
+        return cls(h, order)
+
+    def sizes(self):
+        """(subgraphs, hashes of the representative orderings, rows, hashes of the rows' orderings -- 0 unless kept)"""
+        v = [c_u64() for _ in range(4)]
+        check(lib.sw_markers_sizes(self._h, *[ctypes.byref(x) for x in v]))
+        return tuple(x.value for x in v)
+
+    def _reps_raw(self):
+        n_sg, n_rk, _, _ = self.sizes()
+        reps = np.empty(n_sg, MARKER_REP_DTYPE)
+        offs = np.empty(n_sg + 1, np.uint64)
+        hashes = np.empty(n_rk, np.uint64)
+        check(lib.sw_markers_export(self._h, _ptr(reps), _ptr(offs), _ptr(hashes)))
+        return reps, offs, hashes
+
+    def reps(self):
+        """(reps[MARKER_REP_DTYPE], offsets, hashes): the representative row, n_rep and flags of every subgraph, and the
+        representative orderings as CSR."""
+        reps, offs, hashes = self._reps_raw()
+        offs, hashes = _reorder(offs, hashes, self.order)
+        return reps[self.order], offs, hashes
+
+    def rows(self):
+        """For every subgraph: (rows[MARKER_ROW_DTYPE] ascending by assembly, offsets, hashes of the rows' orderings) -- the
+        reference's ``loc``.  Needs ``keep_rows=True``."""
+        n_sg, _, n_rows, n_rk = self.sizes()
+        row_offs = np.empty(n_sg + 1, np.uint64)
+        rows = np.empty(n_rows, MARKER_ROW_DTYPE)
+        k_offs = np.empty(n_rows + 1, np.uint64)
+        hashes = np.empty(n_rk, np.uint64)
+        check(lib.sw_markers_export_rows(self._h, _ptr(row_offs), _ptr(rows), _ptr(k_offs), _ptr(hashes)))
+        ro, ko = row_offs.astype(np.int64), k_offs.astype(np.int64)
+        out = []
+        for i in self.order.tolist():
+            a, b = ro[i], ro[i + 1]
+            out.append((rows[a:b], (k_offs[a:b + 1] - k_offs[a]), hashes[ko[a]:ko[b]]))
+        return out
+
+    def candidates(self, min_len: int) -> np.ndarray:
+        """Indices of the subgraphs the reference keeps (markers.py:514-517): len >= min_len, neither single nor dup."""
+        reps = self.reps()[0]
+        length = (reps["stop"] - reps["start"]).astype(np.uint32)
+        return np.flatnonzero((length >= min_len) & ((reps["flags"] & (MARKER_SINGLE | MARKER_DUP)) == 0))
+
+    def stats(self) -> dict:
+        c = (c_u64 * 4)()
+        ms = (ctypes.c_double * 4)()
+        check(lib.sw_markers_stats(self._h, c, ms))
+        d = dict(zip(("pairs", "spilled", "largest_pair", "vote_spilled"), (int(x) for x in c)))
+        d.update(count_ms=ms[0], rows_ms=ms[1], vote_ms=ms[2], results_ms=ms[3])
+        return d
+
+    def close(self) -> None:
+        if self._h:
+            lib.sw_markers_free(self._h)
             self._h = None
 
     def __del__(self):
