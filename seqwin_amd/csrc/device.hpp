@@ -266,6 +266,19 @@ void radix_sort_keys64(uint64_t *&keys, uint64_t *&alt, uint64_t n, unsigned beg
 void radix_layout(unsigned bits, unsigned *digit_bits, unsigned *n_passes);
 // keys[i] >> 32 a permutation of 0 .. n-1: grouped by the index bits [low_bits, nbit) in two unstable passes (false: not taken)
 bool radix_unsort_perm(uint64_t *&keys, uint64_t *&alt, uint64_t n, unsigned low_bits, unsigned nbit, hipStream_t stream, uint32_t *d_fail);
+// The same in its parts, for a producer that scatters its words into the first pass's buckets itself (index.hip: k_nodes):
+// radix_unsort_perm_begin tests eligibility (false: not taken, nothing enqueued) and enqueues the set-up of both passes' cursors
+// and tickets -- again before every use of the cursors --; first: keys -> alt by the top digit, second: keys -> alt by the next 8 bits.
+constexpr uint32_t UNSORT_CURSOR_STRIDE = 32;   // the first pass's digit cursors lie 256 B apart (= RS_CURSOR_STRIDE, radix.hip)
+struct UnsortPerm {
+    DevArray<unsigned long long> cur_a, cur_b;   // cur_a[d * UNSORT_CURSOR_STRIDE]: next free place of first-pass digit d
+    DevArray<uint32_t> tickets;
+    unsigned low_bits = 0, hi_bits = 0;          // the first pass's digit: index bits [low_bits + 8, low_bits + 8 + hi_bits)
+    uint32_t n_groups = 0, n_tiles = 0, grid = 0;
+};
+bool radix_unsort_perm_begin(UnsortPerm &u, uint64_t n, unsigned low_bits, unsigned nbit, hipStream_t stream);
+void radix_unsort_perm_first(UnsortPerm &u, const uint64_t *keys, uint64_t *alt, uint64_t n, hipStream_t stream, uint32_t *d_fail);
+void radix_unsort_perm_second(UnsortPerm &u, const uint64_t *keys, uint64_t *alt, uint64_t n, hipStream_t stream, uint32_t *d_fail);
 
 // the edge keys by two unstable bucket passes and an LDS finish per sub-bucket (radix.hip): 0 = ukeys / ucnt / *n_runs written as
 // k_rle_keys + k_drop_sentinel_run leave them, 1 = not done (a sub-bucket above `cap` keys or `slots` distinct keys): `keys`

@@ -245,6 +245,7 @@ constexpr uint32_t NODES_ROW = NODES_THREADS * 2;
 constexpr uint32_t NODES_TILE = NODES_ROW * NODES_ROWS;   // 8192 occurrences: one ticket, one look-back
 constexpr uint32_t UNSORT_BITS = 14;                 // the unsort's last step handles 2^14 consecutive indices in LDS
 constexpr uint32_t UNSORT_RANGE = 1u << UNSORT_BITS;
+constexpr bool UNSORT_FUSED_DEFAULT = true;         // k_nodes scatters the unsort words into the first pass's buckets itself (SCAT, below)
 constexpr uint64_t UNSORT_DIRECT_MAX = 1ull << 25;   // up to here (128 MiB of ranks) the array stays in the 256 MiB Infinity Cache and a
                                                      // direct scatter is as fast (measured: 24 M occurrences 7.74 against 7.84 ms per build;
                                                      // 745 M: 239.0 against 232.3 ms)
@@ -280,7 +281,21 @@ __device__ __forceinline__ unsigned long long interleave32(uint32_t a, uint32_t 
 // assembly (k_adj_pairs).  Needs rec_flag and fewer than 2^31 nodes.
 constexpr uint32_t RANK_REP = 0x80000000u;
 constexpr uint8_t OWNER_DROP = 0xFF;   // owner byte of a key that is no row (record boundary): lands behind the last owner
-template <bool BITS, bool REP>
+// SCAT: the unsort words do not go to uval + s but straight into the buckets of the unsort's first pass (radix_unsort_perm:
+// digit = index bits [dig_shift, ...) under dig_mask, digit d owns the places from d << dig_shift on, claimed through
+// cursor[d * UNSORT_CURSOR_STRIDE]) -- the pass that only regrouped them is gone.  The digit of a word is known with its payload,
+// long before its rank half: a word takes its place among the tile's words of its digit from one returning LDS atomic (order
+// inside a digit is free: one counter per digit for the whole workgroup) in front of the barrier the head counts need anyway,
+// and wave 1 scans the 256 counts and claims the tile's places while wave 0 looks back.  Behind the look-back the words are
+// formed, staged in LDS in digit order, and after ONE further barrier streamed out, consecutive lanes to consecutive places.
+constexpr uint32_t NODES_DIGITS = 256;
+struct NodesScat {
+    uint64_t stage[NODES_TILE];              // 64 KiB: the tile's words in digit order
+    unsigned long long goff[NODES_DIGITS];   // global place of a digit's first word of this tile - its place in the stage
+    uint32_t cnt[NODES_DIGITS];              // words per digit
+    uint32_t lstart[NODES_DIGITS];           // their exclusive sums
+};
+template <bool BITS, bool REP, bool SCAT = false>
 __global__ __launch_bounds__(NODES_THREADS) void k_nodes(const uint32_t *__restrict__ key32, const OccPay *__restrict__ pay, uint64_t n,
                                                uint64_t base, const uint32_t *__restrict__ rec_flag, sw_kmer *__restrict__ kmers,
                                                uint64_t *__restrict__ node_hash, uint32_t *__restrict__ node_start,
@@ -288,12 +303,19 @@ __global__ __launch_bounds__(NODES_THREADS) void k_nodes(const uint32_t *__restr
                                                uint64_t *__restrict__ uval,
                                                unsigned long long *__restrict__ tbits, unsigned long long *__restrict__ nbits,
                                                unsigned long long *__restrict__ tile_state, uint32_t *__restrict__ ticket,
-                                               uint32_t *__restrict__ n_nodes_out, uint32_t *__restrict__ order_bad)
+                                               uint32_t *__restrict__ n_nodes_out, uint32_t *__restrict__ order_bad,
+                                               unsigned long long *__restrict__ cursor, uint32_t dig_shift, uint32_t dig_mask)
 {
     __shared__ uint32_t s_tile, s_excl;
     __shared__ uint32_t s_row[NODES_ROWS * NODES_WAVES];   // heads of (row, wave): counts, then exclusive offsets
     static_assert(NODES_ROWS * NODES_WAVES <= 128, "the (row, wave) group counts are scanned by one wave, two per lane");
     const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    NodesScat *sc = nullptr;
+    if constexpr (SCAT) {
+        __shared__ NodesScat s_scat;
+        sc = &s_scat;
+        if (threadIdx.x < NODES_DIGITS) sc->cnt[threadIdx.x] = 0;
+    }
     if (threadIdx.x == 0) s_tile = atomicAdd(ticket, 1u);
     __syncthreads();
     const uint32_t tile = s_tile;
@@ -350,7 +372,41 @@ __global__ __launch_bounds__(NODES_THREADS) void k_nodes(const uint32_t *__restr
         if (lane == 0) s_row[r * NODES_WAVES + wave] = (uint32_t)__popcll(b0) + (uint32_t)__popcll(b1);
     }
     if (misorder && lane == 0) atomicAdd(order_bad, (uint32_t)__popcll(misorder));   // (never, on a device whose LDS unit serves the lanes of an atomic in lane order)
+    uint32_t drank[NODES_ROWS][2];   // (SCAT) place of a word among the tile's words of its digit
+    if constexpr (SCAT) {
+        // all eight atomics are issued before the barrier below waits for them (one exposed LDS round trip, as in the radix passes)
+#pragma unroll
+        for (int r = 0; r < NODES_ROWS; ++r)
+#pragma unroll
+            for (int e = 0; e < 2; ++e) {
+                drank[r][e] = 0;
+                if (s0 + (uint64_t)r * NODES_ROW + 2 * threadIdx.x + e < n)   // (dead lanes of the last tile contribute nothing)
+                    drank[r][e] = atomicAdd(&sc->cnt[(p[r][e].idx >> dig_shift) & dig_mask], 1u);
+            }
+    }
     __syncthreads();
+    if (SCAT && wave == 1) {
+        // four digits per lane: their exclusive sums, and the tile's places in every digit's range from one atomic add on the
+        // digit's cursor (no counts, no look-back: the indices are a permutation) -- the answers arrive under wave 0's look-back
+        const uint4 c4 = reinterpret_cast<const uint4 *>(sc->cnt)[lane];
+        const uint32_t c[4] = {c4.x, c4.y, c4.z, c4.w};
+        unsigned long long g[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+            g[j] = c[j] ? atomicAdd(&cursor[(size_t)(4 * lane + j) * UNSORT_CURSOR_STRIDE], (unsigned long long)c[j]) : 0ull;
+        uint32_t incl = c[0] + c[1] + c[2] + c[3];
+        for (uint32_t d = 1; d < 64; d <<= 1) {
+            const uint32_t up = __shfl_up(incl, d, 64);
+            if (lane >= d) incl += up;
+        }
+        uint32_t before = incl - (c[0] + c[1] + c[2] + c[3]);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            sc->lstart[4 * lane + j] = before;
+            sc->goff[4 * lane + j] = g[j] - before;
+            before += c[j];
+        }
+    }
     if (wave == 0) {
         // exclusive offsets of the (row, wave) groups (two per lane), the tile's total, then the look-back
         constexpr uint32_t GROUPS = NODES_ROWS * NODES_WAVES;
@@ -396,6 +452,12 @@ __global__ __launch_bounds__(NODES_THREADS) void k_nodes(const uint32_t *__restr
     }
     __syncthreads();
     const uint32_t excl = s_excl;
+    if constexpr (SCAT) {   // place in the stage = first place of the digit + place among its words: eight reads in one round trip
+#pragma unroll
+        for (int r = 0; r < NODES_ROWS; ++r)
+#pragma unroll
+            for (int e = 0; e < 2; ++e) drank[r][e] += sc->lstart[(p[r][e].idx >> dig_shift) & dig_mask];
+    }
 #pragma unroll
     for (int r = 0; r < NODES_ROWS; ++r) {
         const uint64_t s = s0 + (uint64_t)r * NODES_ROW + 2 * threadIdx.x;
@@ -434,7 +496,7 @@ __global__ __launch_bounds__(NODES_THREADS) void k_nodes(const uint32_t *__restr
         }
         if (live1) {
             *reinterpret_cast<uint4 *>(kmers + s) = make_uint4(p[r][0].pos, p[r][0].rec, p[r][1].pos, p[r][1].rec);
-            if (uval)
+            if (!SCAT && uval)
                 *reinterpret_cast<ulonglong2 *>(uval + s) = make_ulonglong2(((uint64_t)p[r][0].idx << 32) | w0,
                                                                           ((uint64_t)p[r][1].idx << 32) | w1);
         } else if (live0) {
@@ -442,7 +504,11 @@ __global__ __launch_bounds__(NODES_THREADS) void k_nodes(const uint32_t *__restr
             km.pos = p[r][0].pos;
             km.record_idx = p[r][0].rec;
             kmers[s] = km;
-            if (uval) uval[s] = ((uint64_t)p[r][0].idx << 32) | w0;   // the unsort's element: index above, node below
+            if (!SCAT && uval) uval[s] = ((uint64_t)p[r][0].idx << 32) | w0;   // the unsort's element: index above, node below
+        }
+        if constexpr (SCAT) {   // the same words, to their digit's part of the stage
+            if (live0) sc->stage[drank[r][0]] = ((uint64_t)p[r][0].idx << 32) | w0;
+            if (live1) sc->stage[drank[r][1]] = ((uint64_t)p[r][1].idx << 32) | w1;
         }
         if (rank_direct) {
             if (live0) rank_direct[p[r][0].idx] = w0;
@@ -475,6 +541,25 @@ __global__ __launch_bounds__(NODES_THREADS) void k_nodes(const uint32_t *__restr
                 }
             }
         }
+    }
+    if constexpr (SCAT) {
+        // The barrier waits for the LDS only: the tile's stores to kmers / the node arrays / the bitmaps stay in flight across it
+        // (__syncthreads() would wait for them first: NOTES.md, "Plain load loops wait for every load...").
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        __builtin_amdgcn_s_barrier();
+        asm volatile("" ::: "memory");
+        const uint32_t cnt_tile = (uint32_t)min((uint64_t)NODES_TILE, n - s0);
+        // (all reads of a round requested before the first is used -- places past cnt_tile hold anything, their digit is masked
+        //  into the table and nothing of them is stored)
+        constexpr int OUT = NODES_TILE / NODES_THREADS;
+        uint64_t word[OUT], at[OUT];
+#pragma unroll
+        for (int j = 0; j < OUT; ++j) word[j] = sc->stage[j * NODES_THREADS + threadIdx.x];
+#pragma unroll
+        for (int j = 0; j < OUT; ++j) at[j] = sc->goff[(uint32_t)(word[j] >> (32 + dig_shift)) & dig_mask] + (j * NODES_THREADS + threadIdx.x);
+#pragma unroll
+        for (int j = 0; j < OUT; ++j)   // (at < n always, for a permutation: a bound for indices that are none -- the order guard has then tripped)
+            if (j * NODES_THREADS + threadIdx.x < cnt_tile && at[j] < n) uval[at[j]] = word[j];
     }
 }
 
@@ -2584,30 +2669,49 @@ uint32_t group_occurrences(PaySort &ps, uint64_t n, uint64_t base, const uint32_
     DevArray<uint32_t> words(4);   // [0] tile tickets, [1] the number of nodes, [2] the unsort's radix passes gave up, [3] order-guard violations
     uint32_t back[3] = {0, 0, 0};  // words 1 .. 3 (read after the unsort has been enqueued)
     if (rank_out && !direct) uv1.alloc(n);
+    unsigned nbit = 1;
+    while (nbit < 32 && (1ull << nbit) < n) ++nbit;          // indices < 2^nbit
+    // The unsort's first pass inside k_nodes (SCAT), wherever radix_unsort_perm would take its two unstable passes
+    // (SEQWIN_AMD_UNSORT_FUSED=0, tests: the two passes behind a plain k_nodes)
+    bool want_fused = UNSORT_FUSED_DEFAULT;
+    if (const char *e = SW_TEST_GETENV("SEQWIN_AMD_UNSORT_FUSED")) want_fused = atoi(e) != 0;
+    UnsortPerm perm;
+    const char *route = !rank_out ? "none" : direct ? "direct" : nbit <= UNSORT_BITS ? "one bucket" : "sort";
     for (int attempt = 0;; ++attempt) {
         SW_HIP(hipMemsetAsync(tile_state.p, 0, (size_t)blocks * 8, stream));
         SW_HIP(hipMemsetAsync(words.p, 0, 16, stream));
+        // (the cursors are set up in front of every launch: the retry below finds them fresh)
+        const bool fused = want_fused && rank_out && !direct && nbit > UNSORT_BITS && sort_keys64_is_own(n) &&
+                           radix_unsort_perm_begin(perm, n, UNSORT_BITS, nbit, stream);
         {
             auto launch = [&](auto kern) {
                 hipLaunchKernelGGL(kern, dim3(blocks), dim3(NODES_THREADS), 0, stream, ps.key32, ps.pay, n, base, rec_flag, ix.kmers.p,
-                                   np.hash.p, np.start.p, direct ? rank_out : (uint32_t *)nullptr, uv0.p, bits ? tbits->p : (unsigned long long *)nullptr,
-                                   bits ? nbits->p : (unsigned long long *)nullptr, tile_state.p, words.p, words.p + 1, words.p + 3);
+                                   np.hash.p, np.start.p, direct ? rank_out : (uint32_t *)nullptr, fused ? uv1.p : uv0.p,
+                                   bits ? tbits->p : (unsigned long long *)nullptr, bits ? nbits->p : (unsigned long long *)nullptr,
+                                   tile_state.p, words.p, words.p + 1, words.p + 3, fused ? perm.cur_a.p : (unsigned long long *)nullptr,
+                                   fused ? perm.low_bits + 8 : 0u, fused ? (1u << perm.hi_bits) - 1u : 0u);
             };
-            if (bits && rep) launch(k_nodes<true, true>);
+            if (fused) {
+                if (bits && rep) launch(k_nodes<true, true, true>);
+                else if (bits) launch(k_nodes<true, false, true>);
+                else if (rep) launch(k_nodes<false, true, true>);
+                else launch(k_nodes<false, false, true>);
+            } else if (bits && rep) launch(k_nodes<true, true>);
             else if (bits) launch(k_nodes<true, false>);
             else if (rep) launch(k_nodes<false, true>);
             else launch(k_nodes<false, false>);
         }
         SW_HIP(hipGetLastError());
         if (rank_out && !direct) {
-            unsigned nbit = 1;
-            while (nbit < 32 && (1ull << nbit) < n) ++nbit;          // indices < 2^nbit
             uint64_t *v = uv0.p;
-            if (nbit > UNSORT_BITS) {   // buckets of 2^14 consecutive indices: sort on the index's bits above those
+            if (fused) {   // the words lie in uv1, grouped by the top digit: the second pass brings them to uv0
+                radix_unsort_perm_second(perm, uv1.p, uv0.p, n, stream, words.p + 2);
+                route = "fused";
+            } else if (nbit > UNSORT_BITS) {   // buckets of 2^14 consecutive indices: sort on the index's bits above those
                 // (begin_bit > 0 of rocPRIM's radix sort is checked on this stack by scripts/micro/sort_beginbit.hip)
                 uint64_t *v_alt = uv1.p;
-                if (!(sort_keys64_is_own(n) && radix_unsort_perm(v, v_alt, n, UNSORT_BITS, nbit, stream, words.p + 2)))
-                    sort_keys64(v, v_alt, n, 32 + UNSORT_BITS, 32 + nbit, stream, words.p + 2, true);   // (the indices are a permutation)
+                if (sort_keys64_is_own(n) && radix_unsort_perm(v, v_alt, n, UNSORT_BITS, nbit, stream, words.p + 2)) route = "two passes";
+                else sort_keys64(v, v_alt, n, 32 + UNSORT_BITS, 32 + nbit, stream, words.p + 2, true);   // (the indices are a permutation)
             }
             if (hold && rep && nbit > UNSORT_BITS && !SW_TEST_GETENV("SEQWIN_AMD_ADJ_SEPARATE")) {
                 hold->sorted = v;
@@ -2619,6 +2723,9 @@ uint32_t group_occurrences(PaySort &ps, uint64_t n, uint64_t base, const uint32_
         }
         SW_HIP(hipMemcpyAsync(back, words.p + 1, 12, hipMemcpyDeviceToHost, stream));
         SW_HIP(hipStreamSynchronize(stream));   // n_nodes has arrived
+        if (getenv("SEQWIN_AMD_DEBUG_NODES"))
+            fprintf(stderr, "[nodes] %llu occurrences (indices of %u bits), attempt %d: unsort route %s, %u nodes, order guard %u\n",
+                    (unsigned long long)n, nbit, attempt, route, back[0], back[2]);
         if (back[2] == 0) break;
         // k_nodes saw occurrences out of (hash, stream index) order: the LDS-atomic ranking of the radix passes did not keep
         // the lane order on this device (or SEQWIN_AMD_FAULT_INJECT=rank).  Nothing of this attempt is kept.

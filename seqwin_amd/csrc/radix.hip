@@ -1263,41 +1263,69 @@ __global__ void k_rs_perm_cursors(unsigned long long *__restrict__ cursor, uint3
 // the second pass owns [.. + (e << low_bits), ...) -- and a tile claims its places with one atomic add per digit: no counting,
 // no scan, no look-back in either pass (an LSD pair of passes needs its second one stable).  Takes two digits of up to 8
 // bits (8 < nbit - low_bits <= 16, tiles of 8192 keys inside one first-pass bucket); returns false otherwise.
-bool radix_unsort_perm(uint64_t *&keys, uint64_t *&alt, uint64_t n, unsigned low_bits, unsigned nbit, hipStream_t stream, uint32_t *d_fail)
+bool radix_unsort_perm_begin(UnsortPerm &u, uint64_t n, unsigned low_bits, unsigned nbit, hipStream_t stream)
 {
     constexpr int THREADS = 512, BITS = 8;
     constexpr uint32_t RADIX = 1u << BITS, TILE = THREADS * RS_ITEMS;
+    static_assert(UNSORT_CURSOR_STRIDE == RS_CURSOR_STRIDE, "one cursor layout for the first pass and for a producer that scatters itself");
     if (n == 0 || nbit <= low_bits + 8 || nbit > low_bits + 16 || SW_AB_GETENV("SEQWIN_AMD_RADIX_STABLE_UNSORT")) return false;
     if ((1ull << (low_bits + 8)) % TILE) return false;
     const char *kind = SW_AB_GETENV("SEQWIN_AMD_RADIX_KERNEL");
     if (kind && !strcmp(kind, "classic")) return false;
-    const unsigned hi_bits = nbit - low_bits - 8;                         // 1 .. 8
-    const uint32_t n_groups = (uint32_t)((n + (1ull << (low_bits + 8)) - 1) >> (low_bits + 8));
+    u.low_bits = low_bits;
+    u.hi_bits = nbit - low_bits - 8;                                      // 1 .. 8
+    u.n_groups = (uint32_t)((n + (1ull << (low_bits + 8)) - 1) >> (low_bits + 8));
     const uint64_t n_tiles = (n + TILE - 1) / TILE;
+    u.n_tiles = (uint32_t)n_tiles;
     int dev = 0, per_cu = 0;
     SW_HIP(hipGetDevice(&dev));
     hipDeviceProp_t prop;
     SW_HIP(hipGetDeviceProperties(&prop, dev));
     SW_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_rs_pass_p<THREADS, BITS, 0>, THREADS, 0));
-    const unsigned grid = (unsigned)std::min<uint64_t>(n_tiles, (uint64_t)std::max(1, per_cu) * std::max(1, prop.multiProcessorCount));
-    DevArray<unsigned long long> cur_a((size_t)RADIX * RS_CURSOR_STRIDE), cur_b((size_t)n_groups * RADIX);
-    DevArray<uint32_t> tickets(2);
-    SW_HIP(hipMemsetAsync(tickets.p, 0, 8, stream));
-    hipLaunchKernelGGL(k_rs_perm_cursors, dim3(1), dim3(RADIX), 0, stream, cur_a.p, 1u, RADIX, RS_CURSOR_STRIDE, 64u, low_bits + 8);
-    hipLaunchKernelGGL(k_rs_perm_cursors, dim3((n_groups * RADIX + 255) / 256), dim3(256), 0, stream, cur_b.p, n_groups, RADIX, 1u,
+    u.grid = (unsigned)std::min<uint64_t>(n_tiles, (uint64_t)std::max(1, per_cu) * std::max(1, prop.multiProcessorCount));
+    if (!u.cur_a.p) {   // (a second set-up -- the order guard's retry -- writes the same buffers again, on the same stream)
+        u.cur_a.alloc((size_t)RADIX * RS_CURSOR_STRIDE);
+        u.cur_b.alloc((size_t)u.n_groups * RADIX);
+        u.tickets.alloc(2);
+    }
+    SW_HIP(hipMemsetAsync(u.tickets.p, 0, 8, stream));
+    hipLaunchKernelGGL(k_rs_perm_cursors, dim3(1), dim3(RADIX), 0, stream, u.cur_a.p, 1u, RADIX, RS_CURSOR_STRIDE, 64u, low_bits + 8);
+    hipLaunchKernelGGL(k_rs_perm_cursors, dim3((u.n_groups * RADIX + 255) / 256), dim3(256), 0, stream, u.cur_b.p, u.n_groups, RADIX, 1u,
                        low_bits + 8, low_bits);
-    // (both passes are unstable -- the order inside a bucket is free --, so they rank by LDS atomics on any device)
-    auto pass = ballot_forced() ? k_rs_pass_p<THREADS, BITS, 0> : k_rs_pass_p<THREADS, BITS, 1>;
-    hipLaunchKernelGGL(pass, dim3(grid), dim3(THREADS), 0, stream, (const uint64_t *)keys, alt, n, (uint32_t)n_tiles,
-                       32u + low_bits + 8, hi_bits, (const unsigned long long *)nullptr, (unsigned long long *)nullptr, tickets.p, d_fail,
-                       0u, cur_a.p, RS_CURSOR_STRIDE, 64u, 0u);
-    std::swap(keys, alt);
-    hipLaunchKernelGGL(pass, dim3(grid), dim3(THREADS), 0, stream, (const uint64_t *)keys, alt, n, (uint32_t)n_tiles, 32u + low_bits,
-                       8u, (const unsigned long long *)nullptr, (unsigned long long *)nullptr, tickets.p + 1, d_fail, 0u, cur_b.p, 1u,
-                       low_bits + 8, 0u);
-    std::swap(keys, alt);
     SW_HIP(hipGetLastError());
     return true;
+}
+
+// (both passes are unstable -- the order inside a bucket is free --, so they rank by LDS atomics on any device)
+void radix_unsort_perm_first(UnsortPerm &u, const uint64_t *keys, uint64_t *alt, uint64_t n, hipStream_t stream, uint32_t *d_fail)
+{
+    constexpr int THREADS = 512, BITS = 8;
+    auto pass = ballot_forced() ? k_rs_pass_p<THREADS, BITS, 0> : k_rs_pass_p<THREADS, BITS, 1>;
+    hipLaunchKernelGGL(pass, dim3(u.grid), dim3(THREADS), 0, stream, keys, alt, n, u.n_tiles, 32u + u.low_bits + 8, u.hi_bits,
+                       (const unsigned long long *)nullptr, (unsigned long long *)nullptr, u.tickets.p, d_fail, 0u, u.cur_a.p,
+                       RS_CURSOR_STRIDE, 64u, 0u);
+    SW_HIP(hipGetLastError());
+}
+
+void radix_unsort_perm_second(UnsortPerm &u, const uint64_t *keys, uint64_t *alt, uint64_t n, hipStream_t stream, uint32_t *d_fail)
+{
+    constexpr int THREADS = 512, BITS = 8;
+    auto pass = ballot_forced() ? k_rs_pass_p<THREADS, BITS, 0> : k_rs_pass_p<THREADS, BITS, 1>;
+    hipLaunchKernelGGL(pass, dim3(u.grid), dim3(THREADS), 0, stream, keys, alt, n, u.n_tiles, 32u + u.low_bits, 8u,
+                       (const unsigned long long *)nullptr, (unsigned long long *)nullptr, u.tickets.p + 1, d_fail, 0u, u.cur_b.p, 1u,
+                       u.low_bits + 8, 0u);
+    SW_HIP(hipGetLastError());
+}
+
+bool radix_unsort_perm(uint64_t *&keys, uint64_t *&alt, uint64_t n, unsigned low_bits, unsigned nbit, hipStream_t stream, uint32_t *d_fail)
+{
+    UnsortPerm u;
+    if (!radix_unsort_perm_begin(u, n, low_bits, nbit, stream)) return false;
+    radix_unsort_perm_first(u, keys, alt, n, stream, d_fail);
+    std::swap(keys, alt);
+    radix_unsort_perm_second(u, keys, alt, n, stream, d_fail);
+    std::swap(keys, alt);
+    return true;   // (the cursors go back to the pool here; their next user is ordered after these kernels on this stream)
 }
 
 bool radix_pairs_available() { return rank_mode() == 1; }   // (the pair passes rank by LDS atomics only)
