@@ -389,7 +389,7 @@ void prefault(const HostSpan *spans, int n_spans)
     size_t total = 0;
     for (int i = 0; i < n_spans; ++i) total += spans[i].p ? spans[i].n : 0;
     const unsigned hw = std::max(1u, std::thread::hardware_concurrency());
-    const unsigned nt = (total >= (32u << 20) && !SW_AB_GETENV("SEQWIN_AMD_NO_PREFAULT")) ? std::min(8u, hw) : 1u;
+    const unsigned nt = total >= (32u << 20) ? std::min(8u, hw) : 1u;
     if (nt <= 1) return;
     std::vector<std::thread> th;
     for (unsigned t = 0; t < nt; ++t)

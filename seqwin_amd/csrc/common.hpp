@@ -16,25 +16,16 @@
 
 #include "../../include/seqwin_hip.h"
 
-// A/B switches.  Alternatives that lost their measurement and are the default for no input (the one-tile-per-workgroup radix
-// pass, the extra tile shapes, the look-back form of the unsort, rocPRIM's run-length pass, the descent sweeps over the payloads,
-// the "tails" tile plan, ...) are compiled OUT of the release library: their environment variables read as
-// unset and their kernels are not instantiated.  `make -C seqwin_amd/csrc ab` builds libseqwin_hip_ab.so with -DSW_AB, where
-// they are live (tests/tools/*_time.py, NOTES.md).  Switches that force a size-dependent DEFAULT path on small inputs (the
-// suite's way of reaching the 15 000-genome branches), debug output and the fault injection stay in the release library.
-#ifdef SW_AB
-#define SW_AB_GETENV(name) getenv(name)
-#else
-#define SW_AB_GETENV(name) ((const char *)nullptr)
-#endif
-
+// Two libraries are built from these sources: the release library (seqwin_amd/libseqwin_hip.so) and the TEST library
+// (`make -C seqwin_amd/csrc test` -> seqwin_amd/libseqwin_hip_test.so, -DSW_TEST_HOOKS: what tests/conftest.py and the fuzzer load).
+//
 // Test hooks (r06): switches that force a path which is the DEFAULT only at sizes no unit test has (how the
 // suite and the fuzzer reach the 15 000-genome branches), the safe alternatives the guards fall back to, the host packer's narrower
-// forms, the fault injection and the lowered index bound.  They are live in the TEST library (`make -C seqwin_amd/csrc test` ->
-// seqwin_amd/libseqwin_hip_test.so, -DSW_TEST_HOOKS: what tests/conftest.py and the fuzzer load) and in the A/B build; in the
-// release library they read as unset -- same kernels, same code, the switches' strings are not even in the binary
-// (tests/test_abi_cpu.py checks that) -- which leaves a deployment the "use" switches of DESIGN.md section 8a only.
-#if defined(SW_TEST_HOOKS) || defined(SW_AB)
+// forms, the fault injection and the lowered index bound.  They are live in the test library only; in the release library they
+// read as unset -- same kernels, same code, the switches' strings are not even in the binary (tests/test_abi_cpu.py checks
+// that) -- which leaves a deployment the "use" switches of DESIGN.md section 8a only.  An alternative that loses its
+// measurement is deleted, not kept behind a switch (NOTES.md records what was and where to find it).
+#ifdef SW_TEST_HOOKS
 #define SW_TEST_GETENV(name) getenv(name)
 #else
 #define SW_TEST_GETENV(name) ((const char *)nullptr)

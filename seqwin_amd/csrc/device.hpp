@@ -149,7 +149,7 @@ struct Plan {
     // Fast tile classes: [0] 256-thread workgroups (256 * L elements per tile), [1] 64-thread workgroups (64 * L) for
     // short records: a tile occupies its workgroup's LDS whatever its fill, so a 1 kbp contig in a 256-thread tile keeps
     // 3 of 4 waves idle and the CU at a quarter of its occupancy.  Every tile carries its own (record, first window end,
-    // global id), so the classes can mix inside a record (get_plan: only behind SEQWIN_AMD_SKETCH=tails, measured slower).
+    // global id); get_plan cuts a record into tiles of ONE class (mixing them inside a record was measured slower).
     struct FastClass {
         uint32_t B = 0;                // threads per workgroup
         uint32_t TW = 0;               // window ends per tile (0 = class unavailable)

@@ -786,10 +786,9 @@ void ingest_fasta(const char *const *paths, size_t n_paths, uint64_t n_cpu, Host
     // quota): 2 048 genomes of 5 Mbp in /dev/shm, FASTA -> numpy at 32 workers (tests/tools/e2e_ingest_ab.py, Gbp/s) -- one box
     // read() 25.7 / mmap 26.9 / mmap + MAP_POPULATE 30.3, the next box 23.6-26.7 / 22.4-27.1 / 16.7-17.5, and inside bench.py on a
     // third 15 (all worker counts alike: serialised).  Not robust across boxes: read() stays.  SEQWIN_AMD_MMAP=0 / 1 / 2 forces
-    // read() / mmap / mmap + populate for such measurements, SEQWIN_AMD_NO_MMAP=1 is read() also for a single worker.
+    // read() / mmap / mmap + populate for such measurements (0: read() also for a single worker).
     int mmap_mode = threaded ? 0 : 1;
     if (const char *e = SW_TEST_GETENV("SEQWIN_AMD_MMAP")) mmap_mode = atoi(e);
-    if (SW_TEST_GETENV("SEQWIN_AMD_NO_MMAP")) mmap_mode = 0;
     const int use_mmap = mmap_mode;
     BufferPool pool;
     if (sink) pool.arena = sink->arena();

@@ -2432,8 +2432,8 @@ void sort_pay(uint64_t n, hipStream_t stream, PaySort &o)
     o.pay_b.alloc(n);
     uint32_t *keys = o.key_a.p, *keys_alt = o.key_b.p;
     OccPay *vals = o.pay_a.p, *vals_alt = o.pay_b.p;
-    bool have_low = false;   // the last pass left the low halves in o.low (SEQWIN_AMD_DESC_LOW=0: A/B, the sweeps read the payloads)
-    const bool want_low = bits == 32 && !(SW_AB_GETENV("SEQWIN_AMD_DESC_LOW") && atoi(SW_AB_GETENV("SEQWIN_AMD_DESC_LOW")) == 0);   // (=0: A/B, -DSW_AB)
+    bool have_low = false;   // the last pass left the low halves in o.low (otherwise the sweeps read the payloads)
+    const bool want_low = bits == 32;
     if (o.staged) {   // (order_tuples made sure: 32 key bits, radix.hip's pair passes)
         OrderedOcc &occ = *o.staged;
         StageSource S{};
@@ -3314,17 +3314,14 @@ void edges_from_pairs(uint64_t *keys, uint64_t *keys_alt, uint64_t m, uint64_t s
     DevArray<uint64_t> ukeys(m);
     DevArray<uint32_t> ucnt(m + 1), ucount(2);   // ucount[1]: places where the sorted keys descend (order guard, r05)
     unsigned long long n_cand = host_n_cand;
-    // run lengths by this library's streaming pass (k_rle_keys: ucnt then holds the START of every run, and m behind the last);
-    // SEQWIN_AMD_RLE=rocprim: rocprim::run_length_encode (ucnt = the lengths) -- A/B, and what rounds 1-3 ran
-    const char *rle_env = SW_AB_GETENV("SEQWIN_AMD_RLE");   // (-DSW_AB builds only)
-    const bool own_rle = !(rle_env && !strcmp(rle_env, "rocprim"));
+    // run lengths by this library's streaming pass (k_rle_keys: ucnt then holds the START of every run, and m behind the last)
     // r07: where every pair has many copies, the keys are grouped by two unstable bucket passes and each sub-bucket is finished in
     // LDS (radix_edge_buckets: no sorted key array, no repair, no run-length pass) -- the packed single-device form, from
     // EDGE_BUCKET_MIN_KEYS keys on and above four keys per node (below, few pairs repeat: the LDS tables of distinct keys overflow
     // and the second skipped digit pays instead, see `skip`).  A sub-bucket beyond the capacities sends the untouched multiset down the radix passes.
-    bool by_buckets = !wide && nb < 32 && own_rle && sort_keys64_is_own(m) && m >= EDGE_BUCKET_MIN_KEYS && ix.n_nodes && m > 4 * ix.n_nodes;
+    bool by_buckets = !wide && nb < 32 && sort_keys64_is_own(m) && m >= EDGE_BUCKET_MIN_KEYS && ix.n_nodes && m > 4 * ix.n_nodes;
     uint32_t bucket_cap = EDGE_BUCKET_CAP, bucket_slots = EDGE_BUCKET_SLOTS;
-    if (const char *e = SW_TEST_GETENV("SEQWIN_AMD_EDGE_SORT")) by_buckets = !wide && nb < 32 && own_rle && !strcmp(e, "bucket");   // tests: either route at any size
+    if (const char *e = SW_TEST_GETENV("SEQWIN_AMD_EDGE_SORT")) by_buckets = !wide && nb < 32 && !strcmp(e, "bucket");   // tests: either route at any size
     if (const char *e = SW_TEST_GETENV("SEQWIN_AMD_EDGE_BUCKET_CAP")) bucket_cap = (uint32_t)strtoul(e, nullptr, 10);
     if (const char *e = SW_TEST_GETENV("SEQWIN_AMD_EDGE_BUCKET_SLOTS")) bucket_slots = (uint32_t)strtoul(e, nullptr, 10);
     if (by_buckets) {
@@ -3351,7 +3348,7 @@ void edges_from_pairs(uint64_t *keys, uint64_t *keys_alt, uint64_t m, uint64_t s
     bool demoted = false;
     for (int attempt = 0; !by_buckets; ++attempt) {
         SW_HIP(hipMemsetAsync(ucount.p + 1, 0, 4, stream));
-        if (own_rle) {
+        {   // (the pass's look-back state goes back to the pool at once: stream-ordered)
             const unsigned blocks = (unsigned)((m + RLE_TILE - 1) / RLE_TILE);
             DevArray<unsigned long long> tile_state(blocks);
             DevArray<uint32_t> ticket(1);
@@ -3360,15 +3357,6 @@ void edges_from_pairs(uint64_t *keys, uint64_t *keys_alt, uint64_t m, uint64_t s
             hipLaunchKernelGGL(k_rle_keys, dim3(blocks), dim3(RLE_THREADS), 0, stream, (const uint64_t *)keys, m, ukeys.p, ucnt.p, tile_state.p,
                                ticket.p, ucount.p, ucount.p + 1);
             SW_HIP(hipGetLastError());
-        } else {
-#ifdef SW_AB
-            hipLaunchKernelGGL(k_check_ascending, dim3(blocks_for(m)), dim3(TPB), 0, stream, (const uint64_t *)keys, m, ucount.p + 1);
-            size_t tmp_bytes = 0;
-            SW_HIP(rocprim::run_length_encode(nullptr, tmp_bytes, keys, m, ukeys.p, ucnt.p, ucount.p, stream));
-            DevArray<unsigned char> tmp(tmp_bytes);
-            SW_HIP(rocprim::run_length_encode(tmp.p, tmp_bytes, keys, m, ukeys.p, ucnt.p, ucount.p, stream));
-            SW_HIP(hipStreamSynchronize(stream));   // (tmp is released here)
-#endif
         }
         hipLaunchKernelGGL(k_drop_sentinel_run, dim3(1), dim3(1), 0, stream, ukeys.p, sentinel, ucount.p);
         SW_HIP(hipGetLastError());
@@ -3410,17 +3398,11 @@ void edges_from_pairs(uint64_t *keys, uint64_t *keys_alt, uint64_t m, uint64_t s
     if (ix.n_edges == 0) return;
     ix.edges.alloc(ix.n_edges);
     if (rank_hash_ready) SW_HIP(hipStreamWaitEvent(stream, rank_hash_ready, 0));   // (rank_hash is written on another stream)
-    if (wide && own_rle)
+    if (wide)
         hipLaunchKernelGGL(k_edges_runs_wide<true>, dim3(blocks_for(ix.n_edges)), dim3(TPB), 0, stream, ukeys.p, ucnt.p, (uint64_t)ix.n_edges,
                            wide->hi_bits, wide->lo_base, wide->hash, ix.edges.p);
-    else if (wide)
-        hipLaunchKernelGGL(k_edges_runs_wide<false>, dim3(blocks_for(ix.n_edges)), dim3(TPB), 0, stream, ukeys.p, ucnt.p, (uint64_t)ix.n_edges,
-                           wide->hi_bits, wide->lo_base, wide->hash, ix.edges.p);
-    else if (own_rle)
-        hipLaunchKernelGGL(k_edges_runs<true>, dim3(blocks_for(ix.n_edges)), dim3(TPB), 0, stream, ukeys.p, ucnt.p, 0u, ~0ull,
-                           (uint64_t)ix.n_edges, nb, ix.nodes.p, rank_hash, ix.edges.p);
     else
-        hipLaunchKernelGGL(k_edges_runs<false>, dim3(blocks_for(ix.n_edges)), dim3(TPB), 0, stream, ukeys.p, ucnt.p, 0u, ~0ull,
+        hipLaunchKernelGGL(k_edges_runs<true>, dim3(blocks_for(ix.n_edges)), dim3(TPB), 0, stream, ukeys.p, ucnt.p, 0u, ~0ull,
                            (uint64_t)ix.n_edges, nb, ix.nodes.p, rank_hash, ix.edges.p);
     SW_HIP(hipGetLastError());
     if (n_cand) {
@@ -3656,7 +3638,7 @@ void build_index(const uint32_t *d_rec_asm, uint64_t n_records, uint64_t n_assem
             DevArray<unsigned long long> ehist;
             unsigned hbits = 0, hpasses = 0;
             uint32_t iters = 1;
-            if (sort_keys64_is_own(m) && !SW_AB_GETENV("SEQWIN_AMD_NO_ADJ_HIST")) {
+            if (sort_keys64_is_own(m)) {
                 radix_layout(2 * nb, &hbits, &hpasses);
                 ehist.alloc((size_t)hpasses << hbits);
                 SW_HIP(hipMemsetAsync(ehist.p, 0, ehist.bytes(), stream));

@@ -101,10 +101,6 @@ template <int BITS> __global__ void k_rs_scan(unsigned long long *__restrict__ h
     if (cursor) cursor[(size_t)threadIdx.x * RS_CURSOR_STRIDE] = s[threadIdx.x] - v;
 }
 
-#ifdef SW_AB   // (records of the one-tile-per-workgroup pass)
-constexpr unsigned long long RS_AGG = 1ull << 62, RS_INC = 2ull << 62, RS_VAL = (1ull << 62) - 1ull;
-#endif
-
 // Lanes of the wave whose digit equals this lane's (among the live ones), as two 32-bit halves: per digit bit one ballot and,
 // per half, one three-input bit operation  m & ~(ballot ^ -bit)  (the compiler's own form of  m &= bit ? bal : ~bal  was nine
 // VALU instructions per bit on 64-bit lane masks -- 107 per key at 9 bits, a third of a pass).
@@ -235,125 +231,8 @@ static uint32_t fault_rank()
     return (e && !strcmp(e, "rank")) ? 1u : 0u;
 }
 
-// One pass: tile t = workgroup t takes THREADS x 16 consecutive keys, wave w of it the w-th 1024 of them, lane l item i the
-// key w * 1024 + i * 64 + l.  Two shapes: 512 threads with 8-bit digits (8192-key tiles, 72 KiB of LDS, two workgroups per CU)
-// and 1024 threads with 9-bit digits (16384-key tiles, 150 KiB: the same 32 keys per digit and tile, one pass fewer for the
-// 54 bits of the edge pairs).  This one-tile-per-workgroup form (SEQWIN_AMD_RADIX_KERNEL=classic; the default is the
-// persistent form below) waits for lower-numbered workgroups: like rocPRIM's onesweep it relies on the dispatcher starting
-// workgroups in index order.  Should a wait ever outlast RS_SPIN_LIMIT polls, the workgroup gives up and raises *fail --
-// the caller then reports an error -- instead of hanging the device.
+// Polls a look-back wait may take before its workgroup gives up (k_rs_pass_p and the pair passes)
 constexpr uint32_t RS_SPIN_LIMIT = 1u << 22;
-#ifdef SW_AB
-template <int THREADS, int BITS>
-__global__ __launch_bounds__(THREADS) void k_rs_pass(const uint64_t *__restrict__ in, uint64_t *__restrict__ out, uint64_t n,
-                                                     unsigned shift, unsigned bits, const unsigned long long *__restrict__ digit_base,
-                                                     unsigned long long *__restrict__ state, uint32_t *__restrict__ fail)
-{
-    constexpr uint32_t RADIX = 1u << BITS, WAVES = THREADS / 64, TILE = THREADS * RS_ITEMS;
-    static_assert(RADIX <= (uint32_t)THREADS, "one thread per digit");
-    __shared__ uint64_t sk[TILE];
-    __shared__ uint16_t whist[WAVES][RADIX];         // per wave: running digit counts (<= 1024), then the wave's base inside the tile's digit
-    __shared__ uint32_t lstart[RADIX];               // first local position of a digit in the tile
-    __shared__ unsigned long long goff[RADIX];       // global position of local position 0 of a digit: out[goff[d] + local]
-    __shared__ uint32_t wsum[RADIX / 64];
-    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
-    for (uint32_t i = tid; i < WAVES * RADIX; i += THREADS) (&whist[0][0])[i] = 0;
-    __syncthreads();
-    const uint32_t tile = blockIdx.x;
-    const uint64_t t0 = (uint64_t)tile * TILE;
-    const uint32_t cnt_tile = (uint32_t)min((uint64_t)TILE, n - t0);
-    const uint32_t dmask = (1u << bits) - 1u;
-
-    uint64_t key[RS_ITEMS];
-    uint32_t rank[RS_ITEMS];   // position of the item among the items of its digit in its wave
-#pragma unroll
-    for (int i = 0; i < RS_ITEMS; ++i) {
-        const uint32_t li = wave * (64 * RS_ITEMS) + i * 64 + lane;
-        key[i] = li < cnt_tile ? in[t0 + li] : ~0ull;
-    }
-#pragma unroll
-    for (int i = 0; i < RS_ITEMS; ++i) {
-        const uint32_t li = wave * (64 * RS_ITEMS) + i * 64 + lane;
-        const bool live = li < cnt_tile;
-        const uint32_t d = (uint32_t)(key[i] >> shift) & dmask;
-        uint32_t mlo, mhi;                                 // lanes with the same digit (among the live ones)
-        match_digit<BITS>(d, live, mlo, mhi);
-        const uint32_t below = __builtin_amdgcn_mbcnt_hi(mhi, __builtin_amdgcn_mbcnt_lo(mlo, 0u));   // ... in lower lanes
-        uint32_t prior = 0;
-        if (live) prior = whist[wave][d];                  // every lane of a group reads before its leader adds
-        rank[i] = prior + below;
-        __builtin_amdgcn_wave_barrier();
-        if (live && below == 0) whist[wave][d] = (uint16_t)(prior + (uint32_t)__popc(mlo) + (uint32_t)__popc(mhi));   // the group's first lane
-        __builtin_amdgcn_wave_barrier();
-    }
-    __syncthreads();
-    // thread d < RADIX: the digit's counts per wave -> bases, total; publish; scan over the digits; look back
-    uint32_t total = 0, incl = 0;
-    unsigned long long *st = state + (size_t)tile * RADIX;
-    if (tid < RADIX) {
-        const uint32_t d = tid;
-#pragma unroll
-        for (uint32_t w = 0; w < WAVES; ++w) {
-            const uint32_t c = whist[w][d];
-            whist[w][d] = (uint16_t)total;
-            total += c;
-        }
-        __hip_atomic_store(&st[d], (tile == 0 ? RS_INC : RS_AGG) | total, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        incl = total;
-        for (uint32_t dd = 1; dd < 64; dd <<= 1) {
-            const uint32_t up = __shfl_up(incl, dd, 64);
-            if (lane >= dd) incl += up;
-        }
-        if (lane == 63) wsum[wave] = incl;
-    }
-    __syncthreads();
-    if (tid < RADIX) {
-        const uint32_t d = tid;
-        uint32_t before = incl - total;
-        for (uint32_t w = 0; w < wave; ++w) before += wsum[w];
-        lstart[d] = before;
-        unsigned long long excl = 0;
-        if (tile) {
-            for (int64_t t = (int64_t)tile - 1; t >= 0; --t) {
-                unsigned long long v;
-                uint32_t spins = 0;
-                for (;;) {
-                    v = __hip_atomic_load(&state[(size_t)t * RADIX + d], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    if ((v >> 62) != 0) break;           // the predecessor started earlier: it will publish
-                    if (++spins > RS_SPIN_LIMIT) {         // (never seen; see above)
-                        atomicOr(fail, 1u);
-                        v = RS_INC;
-                        break;
-                    }
-                    __builtin_amdgcn_s_sleep(1);
-                }
-                excl += v & RS_VAL;
-                if ((v >> 62) == 2) break;
-            }
-            __hip_atomic_store(&st[d], RS_INC | (excl + total), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-        goff[d] = digit_base[d] + excl - before;
-    }
-    __syncthreads();
-#pragma unroll
-    for (int i = 0; i < RS_ITEMS; ++i) {
-        const uint32_t li = wave * (64 * RS_ITEMS) + i * 64 + lane;
-        if (li < cnt_tile) {
-            const uint32_t d = (uint32_t)(key[i] >> shift) & dmask;
-            sk[lstart[d] + whist[wave][d] + rank[i]] = key[i];
-        }
-    }
-    __syncthreads();
-#pragma unroll
-    for (int j = 0; j < RS_ITEMS; ++j) {
-        const uint32_t t = j * THREADS + tid;
-        if (t < cnt_tile) {
-            const uint64_t k = sk[t];
-            out[goff[(uint32_t)(k >> shift) & dmask] + t] = k;
-        }
-    }
-}
-#endif   // SW_AB (the one-tile-per-workgroup pass)
 
 // Look-back records of the persistent passes carry a 16-bit epoch (the pass number of their state buffer) above flag and count:
 // a record of an earlier pass -- or of an earlier sort -- reads as "not published", so the buffer is never cleared between passes
@@ -369,14 +248,21 @@ __device__ __forceinline__ uint32_t rse_flag(unsigned long long w, uint32_t epoc
     return (uint32_t)(w >> 48) == epoch ? (uint32_t)(w >> 46) & 3u : 0u;
 }
 
-// The same pass as a PERSISTENT kernel: a workgroup takes tiles from a ticket counter until none are left, and the keys of
-// its next tile are already on their way (registers) while it ranks, scans and writes the current one -- with one workgroup
-// of 150 KiB per CU the one-tile-per-workgroup form leaves the memory pipe idle during ranking and look-back and the ALUs idle
-// during the loads (2.7 TB/s of moved bytes against 4.5 for rocPRIM's 20-byte pair passes).  Tickets also make the look-back
+// One pass: a tile is THREADS x 16 consecutive keys, wave w of the workgroup takes the w-th 1024 of them, lane l item i the
+// key w * 1024 + i * 64 + l.  Two shapes: 512 threads with 8-bit digits (8192-key tiles, 72 KiB of LDS, two workgroups per CU)
+// and 1024 threads with 9-bit digits (16384-key tiles, 150 KiB: the same 32 keys per digit and tile, one pass fewer for the
+// 54 bits of the edge pairs).
+//
+// The kernel is PERSISTENT: a workgroup takes tiles from a ticket counter until none are left, and the keys of its next tile
+// are already on their way (registers) while it ranks, scans and writes the current one -- with one workgroup of 150 KiB per
+// CU, one tile per workgroup left the memory pipe idle during ranking and look-back and the ALUs idle during the loads
+// (2.7 TB/s of moved bytes against 4.5 for rocPRIM's 20-byte pair passes).  Tickets also make the look-back
 // independent of the dispatch order: the lowest unfinished tile is always the CURRENT tile of a running workgroup (every
 // workgroup takes its tickets in increasing order and holds at most the current and the next one), so the waits terminate
-// whatever the residency.  The next tile's loads are issued once the current keys sit in LDS -- into the same registers -- and
-// are in flight during the look-back and the write-out; the look-back reads RS_LOOK predecessors per step (independent loads).
+// whatever the residency.  Should a wait ever outlast RS_SPIN_LIMIT polls all the same, the workgroup gives up and raises
+// *fail -- the caller then reports an error -- instead of hanging the device.  The next tile's loads are issued once the
+// current keys sit in LDS -- into the same registers -- and are in flight during the look-back and the write-out; the
+// look-back reads RS_LOOK predecessors per step (independent loads).
 //
 // RANK = 1 (default where the device passes k_rs_rank_selftest): a key's place among the keys of its digit in its wave comes
 // from ONE LDS atomic with return on the wave's counter of that digit (two 16-bit counters per word: a wave holds 1024 keys)
@@ -1136,17 +1022,15 @@ void sort_passes(uint64_t *&keys, uint64_t *&alt, uint64_t n, unsigned begin_bit
     constexpr uint32_t RADIX = 1u << BITS, TILE = THREADS * RS_ITEMS;
     const unsigned n_passes = (end_bit - begin_bit + BITS - 1) / BITS;
     const uint64_t n_tiles = (n + TILE - 1) / TILE;
-    const char *kind = SW_AB_GETENV("SEQWIN_AMD_RADIX_KERNEL");   // A/B (-DSW_AB): "classic" = one tile per workgroup
-    const bool persistent = !(kind && !strcmp(kind, "classic"));
     uint32_t dbg = 0;
 #ifdef SW_RADIX_ABLATION     // timing experiments only (tests/tools/sort_time.py with SEQWIN_AMD_RADIX_DEBUG; the output is NOT sorted): 1 no look-back, 2 no stores, 4 no loads, 8 no ranking
     if (const char *e = getenv("SEQWIN_AMD_RADIX_DEBUG")) dbg = (uint32_t)atoi(e) & 15u;
 #endif
     if (fault_rank()) dbg |= 16u;
-    // resident workgroups of the persistent form (per template instance; taken from the first device that sorts -- any number
-    // is correct, tiles are handed out by tickets)
+    // resident workgroups (per template instance; taken from the first device that sorts -- any number is correct, tiles are
+    // handed out by tickets)
     int grid_p = 0;
-    if (persistent) {
+    {
         static std::mutex &mu = *new std::mutex;                          // leaked on purpose (see api.hip: pool())
         static std::map<int, int> &grids = *new std::map<int, int>;       // per device (and per template instance)
         int dev = 0;
@@ -1162,13 +1046,11 @@ void sort_passes(uint64_t *&keys, uint64_t *&alt, uint64_t n, unsigned begin_bit
         }
         grid_p = g;
     }
-    const bool atomic_rank = persistent && rank_mode() == 1;
-    DevArray<unsigned long long> hist_own(d_hist_given ? 0 : (size_t)n_passes * RADIX), state(persistent ? 0 : (size_t)n_tiles * RADIX);
-    std::unique_ptr<StateUse> su(persistent ? new StateUse(state_buf(stream, (size_t)n_tiles * RADIX)) : nullptr);   // (epoch-tagged records: never cleared per pass)
-    StateBuf *sb = su ? &su->b : nullptr;
+    const bool atomic_rank = rank_mode() == 1;
+    DevArray<unsigned long long> hist_own(d_hist_given ? 0 : (size_t)n_passes * RADIX);
+    StateUse su(state_buf(stream, (size_t)n_tiles * RADIX));   // (epoch-tagged records: never cleared per pass)
     struct { unsigned long long *p; } hist{d_hist_given ? d_hist_given : hist_own.p};   // ([pass][digit] counts; scanned in place below)
-    const bool unstable = perm_hi32 && persistent && !SW_AB_GETENV("SEQWIN_AMD_RADIX_STABLE_UNSORT");   // (A/B, -DSW_AB: the look-back form)
-    DevArray<unsigned long long> cursor(unstable ? (size_t)RADIX * RS_CURSOR_STRIDE : 0);
+    DevArray<unsigned long long> cursor(perm_hi32 ? (size_t)RADIX * RS_CURSOR_STRIDE : 0);
     DevArray<uint32_t> tickets(n_passes);
     SW_HIP(hipMemsetAsync(tickets.p, 0, tickets.bytes(), stream));
     if (d_hist_given) {
@@ -1184,7 +1066,7 @@ void sort_passes(uint64_t *&keys, uint64_t *&alt, uint64_t n, unsigned begin_bit
 #ifdef SW_RS_STAMPS
     DevArray<unsigned long long> stamps;
     const size_t n_st = (size_t)(n_tiles / 64 + 1) * 16;
-    if (getenv("SEQWIN_AMD_STAMPS") && persistent) stamps.alloc(n_st);
+    if (getenv("SEQWIN_AMD_STAMPS")) stamps.alloc(n_st);
 #endif
     for (unsigned p = 0; p < n_passes; ++p) {
         const unsigned sh = begin_bit + BITS * p, bits = std::min<unsigned>(BITS, end_bit - sh);
@@ -1195,26 +1077,19 @@ void sort_passes(uint64_t *&keys, uint64_t *&alt, uint64_t n, unsigned begin_bit
             SW_HIP(hipMemcpyToSymbolAsync(HIP_SYMBOL(g_rs_stamps), &ptr, sizeof ptr, 0, hipMemcpyHostToDevice, stream));
         }
 #endif
-        // (only the FIRST pass may be unstable: the later ones must keep the order the earlier ones made)
-        unsigned long long *cur = unstable && p == 0 ? cursor.p : nullptr;
+        // (a permutation's first pass is unstable -- atomic cursors, its order inside a digit is free --; only the FIRST pass may
+        // be: the later ones must keep the order the earlier ones made)
+        unsigned long long *cur = perm_hi32 && p == 0 ? cursor.p : nullptr;
         hipLaunchKernelGGL(k_rs_scan<BITS>, dim3(1), dim3(RADIX), 0, stream, hist.p + (size_t)p * RADIX, cur);
-        if (!cur && !persistent) SW_HIP(hipMemsetAsync(state.p, 0, state.bytes(), stream));
-        if (persistent) {
-            const uint32_t epoch = cur ? 0u : next_epoch(*sb, stream);
-            auto launch = [&](auto kern) {
-                hipLaunchKernelGGL(kern, dim3((unsigned)std::min<uint64_t>(n_tiles, (uint64_t)grid_p)), dim3(THREADS), 0, stream, keys, alt, n,
-                                   (uint32_t)n_tiles, sh, bits, hist.p + (size_t)p * RADIX, sb->p, tickets.p + p, d_fail, dbg, cur,
-                                   RS_CURSOR_STRIDE, 64u, epoch);
-            };
-            // (an unstable pass may rank by atomics on any device: the order inside a digit is free there)
-            if (cur ? !ballot_forced() : atomic_rank) launch(k_rs_pass_p<THREADS, BITS, 1>);
-            else launch(k_rs_pass_p<THREADS, BITS, 0>);
-        } else {
-#ifdef SW_AB
-            hipLaunchKernelGGL((k_rs_pass<THREADS, BITS>), dim3((unsigned)n_tiles), dim3(THREADS), 0, stream, keys, alt, n, sh, bits,
-                               hist.p + (size_t)p * RADIX, state.p, d_fail);
-#endif
-        }
+        const uint32_t epoch = cur ? 0u : next_epoch(su.b, stream);
+        auto launch = [&](auto kern) {
+            hipLaunchKernelGGL(kern, dim3((unsigned)std::min<uint64_t>(n_tiles, (uint64_t)grid_p)), dim3(THREADS), 0, stream, keys, alt, n,
+                               (uint32_t)n_tiles, sh, bits, hist.p + (size_t)p * RADIX, su.b.p, tickets.p + p, d_fail, dbg, cur,
+                               RS_CURSOR_STRIDE, 64u, epoch);
+        };
+        // (an unstable pass may rank by atomics on any device: the order inside a digit is free there)
+        if (cur ? !ballot_forced() : atomic_rank) launch(k_rs_pass_p<THREADS, BITS, 1>);
+        else launch(k_rs_pass_p<THREADS, BITS, 0>);
         SW_HIP(hipGetLastError());
 #ifdef SW_RS_STAMPS
         if (stamps.p) {
@@ -1239,7 +1114,7 @@ void sort_passes(uint64_t *&keys, uint64_t *&alt, uint64_t n, unsigned begin_bit
 #endif
         std::swap(keys, alt);
     }
-    // (hist / state go back to the pool here; their next user is ordered after these kernels on this stream)
+    // (hist / cursor / tickets go back to the pool here; their next user is ordered after these kernels on this stream)
 }
 
 }  // namespace
@@ -1268,10 +1143,8 @@ bool radix_unsort_perm_begin(UnsortPerm &u, uint64_t n, unsigned low_bits, unsig
     constexpr int THREADS = 512, BITS = 8;
     constexpr uint32_t RADIX = 1u << BITS, TILE = THREADS * RS_ITEMS;
     static_assert(UNSORT_CURSOR_STRIDE == RS_CURSOR_STRIDE, "one cursor layout for the first pass and for a producer that scatters itself");
-    if (n == 0 || nbit <= low_bits + 8 || nbit > low_bits + 16 || SW_AB_GETENV("SEQWIN_AMD_RADIX_STABLE_UNSORT")) return false;
+    if (n == 0 || nbit <= low_bits + 8 || nbit > low_bits + 16) return false;
     if ((1ull << (low_bits + 8)) % TILE) return false;
-    const char *kind = SW_AB_GETENV("SEQWIN_AMD_RADIX_KERNEL");
-    if (kind && !strcmp(kind, "classic")) return false;
     u.low_bits = low_bits;
     u.hi_bits = nbit - low_bits - 8;                                      // 1 .. 8
     u.n_groups = (uint32_t)((n + (1ull << (low_bits + 8)) - 1) >> (low_bits + 8));
@@ -2018,15 +1891,12 @@ int radix_edge_buckets(uint64_t *&keys, uint64_t *&alt, uint64_t m, unsigned key
     return 0;
 }
 
-// which shape a sort of `bits` key bits takes: 0 = 512 threads x 8 bits, 1 = 1024 x 9, 2 = 1024 x 8, 3 = 512 x 9, 4 = 256 x 8 (the last three: A/B)
+// which shape a sort of `bits` key bits takes: 0 = 512 threads x 8 bits, 1 = 1024 x 9
+// (the shapes that lost: 1024 x 8 bits 28.3 ms, 512 x 9 bits 35.5 ms against 25.1 on 745 M 54-bit keys, NOTES.md)
 static int pick_shape(unsigned bits)
 {
-    const char *e = SW_TEST_GETENV("SEQWIN_AMD_RADIX_BITS");   // A/B: 8 or 9
+    const char *e = SW_TEST_GETENV("SEQWIN_AMD_RADIX_BITS");   // (tests: 8 or 9)
     const bool nine = e ? atoi(e) == 9 : (bits + 8) / 9 < (bits + 7) / 8;   // 9-bit digits where they save a pass (54 bits: 6 for 7)
-    const char *shape = SW_AB_GETENV("SEQWIN_AMD_RADIX_SHAPE");   // A/B (-DSW_AB)
-    if (shape && !strcmp(shape, "1024x8")) return 2;
-    if (shape && !strcmp(shape, "512x9")) return 3;
-    if (shape && !strcmp(shape, "256x8")) return 4;
     return nine ? 1 : 0;
 }
 
@@ -2036,7 +1906,7 @@ static int pick_shape(unsigned bits)
 void radix_layout(unsigned bits, unsigned *digit_bits, unsigned *n_passes)
 {
     const int sh = pick_shape(bits);
-    *digit_bits = (sh == 1 || sh == 3) ? 9u : 8u;
+    *digit_bits = sh == 1 ? 9u : 8u;
     *n_passes = (bits + *digit_bits - 1) / *digit_bits;
 }
 
@@ -2050,11 +1920,6 @@ void radix_sort_keys64(uint64_t *&keys, uint64_t *&alt, uint64_t n, unsigned beg
     if (end_bit - begin_bit > 64) raise(SW_ERR_RUNTIME, "radix_sort_keys64: more than 64 key bits");
     // (layout_bits: the upper passes of a radix_layout(layout_bits) sort -- same digit width, begin_bit on a digit boundary)
     switch (pick_shape(layout_bits ? layout_bits : end_bit - begin_bit)) {
-#ifdef SW_AB   // (the shapes that lost: 1024 x 8 bits 28.3 ms, 512 x 9 bits 35.5 ms against 25.1 on 745 M 54-bit keys, NOTES.md)
-    case 2: sort_passes<1024, 8>(keys, alt, n, begin_bit, end_bit, stream, d_fail, perm_hi32, d_hist_given); break;
-    case 3: sort_passes<512, 9>(keys, alt, n, begin_bit, end_bit, stream, d_fail, perm_hi32, d_hist_given); break;
-    case 4: sort_passes<256, 8>(keys, alt, n, begin_bit, end_bit, stream, d_fail, perm_hi32, d_hist_given); break;
-#endif
     case 1: sort_passes<1024, 9>(keys, alt, n, begin_bit, end_bit, stream, d_fail, perm_hi32, d_hist_given); break;
     default: sort_passes<512, 8>(keys, alt, n, begin_bit, end_bit, stream, d_fail, perm_hi32, d_hist_given); break;
     }

@@ -1321,11 +1321,6 @@ Plan &get_plan(sw_batch &b, uint64_t k64, uint64_t w64, bool *cached)
     seg_pos.reserve(R);
     seg_idx.reserve(R);
     uint64_t tiles = 0, tiles_g = 0, tiles0 = 0, tiles1 = 0;
-#ifdef SW_AB
-    const bool tails = force && !strcmp(force, "tails");
-#else
-    const bool tails = false;   // (A/B loser: -DSW_AB builds only)
-#endif
     for (size_t r = 0; r < R; ++r) {
         rec_seg_off[r] = (uint32_t)seg_pos.size();
         rec_tile_off[r] = (uint32_t)tiles;
@@ -1349,21 +1344,18 @@ Plan &get_plan(sw_batch &b, uint64_t k64, uint64_t w64, bool *cached)
             // time whatever its fill, and a 64-thread tile costs about a third of a 256-thread one (measured,
             // tests/tools/fragment_timing.py: 3.6-4.1 ns against 11.0-12.5 ns per tile).  A record is cut, whichever is
             // cheaper in tile count x cost, into (a) 256-thread tiles or (c) 64-thread tiles only.  (b) -- full 256-thread
-            // tiles + 64-thread tiles for the tail -- is implemented (every tile carries its own descriptor) but measured
-            // SLOWER on the default workload (96 kbp contigs, 12 + 1 tiles instead of 13: 3.85 against 3.72 ms): a nearly empty
-            // 256-thread tile leaves the VALU to its neighbours and costs well under a full one, so the model above does not
-            // hold for tails; it stays behind SEQWIN_AMD_SKETCH=tails for experiments.
+            // tiles + 64-thread tiles for the tail -- was measured SLOWER on the default workload (96 kbp contigs, 12 + 1 tiles
+            // instead of 13: 3.85 against 3.72 ms) and is gone: a nearly empty 256-thread tile leaves the VALU to its neighbours
+            // and costs well under a full one, so the model above does not hold for tails.
             bool fast = false;
             uint64_t n_big = 0, n_small = 0;
             if (p.Lf) {
                 const uint64_t TW0 = p.fc[0].TW, TW1 = p.fc[1].TW;
                 const uint64_t nb = windows / TW0, rem = windows % TW0;
                 const uint64_t cost_a = (nb + (rem ? 1 : 0)) * 100;
-                const uint64_t cost_b = (TW1 && tails) ? nb * 100 + (rem + TW1 - 1) / TW1 * 32 : ~0ull;
                 const uint64_t cost_c = TW1 ? (windows + TW1 - 1) / TW1 * 32 : ~0ull;
                 n_big = nb + (rem ? 1 : 0);                                                                  // (a)
-                if (cost_b < cost_a && cost_b <= cost_c) { n_big = nb; n_small = (rem + TW1 - 1) / TW1; }   // (b)
-                else if (cost_c < cost_a) { n_big = 0; n_small = (windows + TW1 - 1) / TW1; }               // (c)
+                if (cost_c < cost_a) { n_big = 0; n_small = (windows + TW1 - 1) / TW1; }                      // (c)
                 // a record with invalid bases is cut into the same tiles; those whose reach [E0, I1) crosses a gap are
                 // listed for the generic kernel's list mode (the fast kernels skip them) -- unless most of its tiles
                 // would be, then the whole record goes to the generic class.  Only such records are walked tile by tile here.
