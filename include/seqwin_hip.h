@@ -364,6 +364,42 @@ int sw_markers_export_rows(const sw_markers *m, uint64_t *row_offsets, sw_marker
 int sw_markers_stats(const sw_markers *m, uint64_t *counters, double *ms);
 void sw_markers_free(sw_markers *m);
 
+/* ---- Assemblies.mash (src/seqwin/assemblies.py:76-99) on the device (csrc/minhash.hip) ---------------------------------------
+ * MinHash sketches as `mash sketch -k K -s S` makes them, one per assembly, and the counts `mash dist` derives for a pair, by the
+ * specification of DESIGN.md section 3 (Mash 2.x at its defaults; tests/tools/minhash_host.py restates it -- the `mash` binary
+ * itself has never been compared).  Hash: MurmurHash3_x64_128 over the k upper-case ASCII bytes of the canonical k-mer, its first
+ * 8 bytes for k >= 17, its first 4 for k <= 16 (a 32-bit sketch).  A sketch: the s smallest distinct hashes of the assembly,
+ * ascending.  A pair: the two ascending lists are walked together until s distinct values were seen or a list ran out -- shared =
+ * the values met in both, total = the values seen, completed by what is left of either list and clamped to s. */
+typedef struct sw_minhash sw_minhash; /* opaque device-resident sketches in CSR form */
+/* Replaces `mash sketch` (mash.sketch as Assemblies.mash calls it, assemblies.py:89-96) over a RESIDENT batch: one sketch per
+ * assembly.  k outside 1..32 (Mash refuses it too), s = 0 or above 2^32 - 1, seed above 2^32 - 1 (Mash's default: 42), a NULL
+ * handle -> SW_ERR_VALUE.  `stream` is a hipStream_t (0 = default stream); the call returns with the sketches finished. */
+int sw_batch_minhash(const sw_batch *batch, uint64_t k, uint64_t s, uint64_t seed, void *stream, sw_minhash **out);
+/* The sketches given as host arrays (what a .msh file holds): sketch a = hashes[offsets[a] .. offsets[a + 1]), hash_bits 32 or
+ * 64.  SW_ERR_VALUE for a list that is not strictly ascending, is longer than s, or -- at 32 bits -- holds a value above
+ * 2^32 - 1 (checked on the host, before a device is touched).  The same pair and reduce core then works on them. */
+int sw_minhash_from_sketches(const uint64_t *offsets, const uint64_t *hashes, uint64_t n, uint64_t s, uint64_t hash_bits,
+                             sw_minhash **out);
+/* Sketches, hashes of all sketches, s, hash_bits (any pointer may be NULL). */
+int sw_minhash_sizes(const sw_minhash *h, uint64_t *n, uint64_t *n_hashes, uint64_t *s, uint64_t *hash_bits);
+/* D2H copies (either may be NULL): offsets[n + 1], hashes[n_hashes] (32-bit sketches widened to uint64). */
+int sw_minhash_export(const sw_minhash *h, uint64_t *offsets, uint64_t *hashes);
+/* Replaces `mash dist` + the parse of its text (mash.get_jaccard as assemblies.py:97-99 consumes it) for rows [r0, r1) against
+ * columns [c0, c1): shared / total of pair (r, c) at [(r - r0) * (c1 - c0) + (c - c0)] of the two host arrays; Jaccard is their
+ * quotient.  Two empty sketches give (0, 0).  A range outside the sketches or r0 > r1 -> SW_ERR_VALUE. */
+int sw_minhash_counts(const sw_minhash *h, uint64_t r0, uint64_t r1, uint64_t c0, uint64_t c1, uint32_t *shared, uint32_t *total);
+/* kmers._expected_frac (src/seqwin/kmers.py:315-323) of the same block, up to the final mean: rowsums[r - r0] = sum over the
+ * row's columns of 2J / (1 + J), J = shared / total in f64, added in a fixed order (the same call twice gives the same bits); the
+ * caller adds the rows and divides by the number of pairs.  A 0 / 0 pair in the block fails the call: SW_ERR_VALUE, "division by
+ * zero" in the message. */
+int sw_minhash_frac_rowsums(const sw_minhash *h, uint64_t r0, uint64_t r1, uint64_t c0, uint64_t c1, double *rowsums);
+/* counters[4] = { assemblies finished by the general route (all k-mers hashed, sorted, first s distinct), candidates kept by the
+ * pre-selection, largest candidate count of an assembly, capacity of an assembly's candidate range }; ms[2] = { hash + pre-select
+ * pass, selection with the general route } (HIP events).  All 0 for sketches given as host arrays. */
+int sw_minhash_stats(const sw_minhash *h, uint64_t *counters, double *ms);
+void sw_minhash_free(sw_minhash *h);
+
 /* ---- multi-GPU merge (one process per GPU; the exchange itself is done by the host side with
  *      torch.distributed / RCCL on the device buffers below).  Together these replace
  *      merge_thread_graphs (cpp/src/seqwin/build_internals.cpp:295-392) across GPUs. -------------- */

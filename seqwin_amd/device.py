@@ -113,6 +113,14 @@ class Batch:
                                  ctypes.byref(h)))
         return Index(h)
 
+    def minhash(self, kmerlen: int, sketchsize: int = 1000, seed: int = 42, stream: int = 0) -> "MinHash":
+        """One MinHash sketch per assembly as ``mash sketch -k kmerlen -s sketchsize`` makes it (csrc/minhash.hip), from the
+        resident packed bases.  ValueError for a k-mer length outside 1..32, as Mash refuses it."""
+        h = c_vp()
+        check(lib.sw_batch_minhash(self._h, c_u64(int(kmerlen)), c_u64(int(sketchsize)), c_u64(int(seed)), c_vp(stream),
+                                   ctypes.byref(h)))
+        return MinHash(h)
+
     def close(self) -> None:
         if self._h:
             lib.sw_batch_free(self._h)
@@ -440,6 +448,126 @@ class Markers:
     def close(self) -> None:
         if self._h:
             lib.sw_markers_free(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _block_range(r, n: int):
+    """None, (lo, hi), a slice or a range of step 1 -> (lo, hi)."""
+    if r is None:
+        return 0, n
+    if isinstance(r, slice):
+        lo, hi, step = r.indices(n)
+        r = range(lo, max(hi, lo), step)
+    if isinstance(r, range):
+        if r.step != 1:
+            raise ValueError("rows / cols must be contiguous")
+        return r.start, max(r.stop, r.start)
+    lo, hi = r
+    return int(lo), int(hi)
+
+
+class MinHash:
+    """MinHash sketches of a set of assemblies, resident on the device (:meth:`Batch.minhash`, :meth:`from_sketches`), and the
+    pair counts ``mash dist`` derives from them: what ``Assemblies.mash`` (src/seqwin/assemblies.py:76-99) gets from the Mash
+    binary.  ``rows`` / ``cols`` are None (all), a ``(lo, hi)`` pair, a slice or a range."""
+
+    def __init__(self, handle: c_vp):
+        self._h = handle
+
+    @classmethod
+    def from_sketches(cls, offsets, hashes, sketchsize: int, hash_bits: int = 64) -> "MinHash":
+        """Sketches given as host arrays in CSR form: strictly ascending lists of at most ``sketchsize`` values."""
+        offs = np.ascontiguousarray(offsets, np.uint64)
+        hs = np.ascontiguousarray(hashes, np.uint64)
+        if offs.ndim != 1 or len(offs) < 1 or int(offs[-1]) != len(hs):
+            raise ValueError("offsets needs one entry per sketch and one more, and offsets[-1] == len(hashes)")
+        h = c_vp()
+        check(lib.sw_minhash_from_sketches(_ptr(offs), _ptr(hs), c_u64(len(offs) - 1), c_u64(int(sketchsize)), c_u64(int(hash_bits)),
+                                           ctypes.byref(h)))
+        return cls(h)
+
+    def sizes(self):
+        """(sketches, hashes of all sketches, sketch size, hash bits)"""
+        v = [c_u64() for _ in range(4)]
+        check(lib.sw_minhash_sizes(self._h, *[ctypes.byref(x) for x in v]))
+        return tuple(x.value for x in v)
+
+    def __len__(self) -> int:
+        return self.sizes()[0]
+
+    def sketches(self):
+        """(offsets[n + 1], hashes): sketch a is hashes[offsets[a]:offsets[a + 1]], ascending, uint64."""
+        n, nh, _, _ = self.sizes()
+        offs = np.empty(n + 1, np.uint64)
+        hs = np.empty(nh, np.uint64)
+        check(lib.sw_minhash_export(self._h, _ptr(offs), _ptr(hs)))
+        return offs, hs
+
+    def counts(self, rows=None, cols=None):
+        """(shared, total): uint32[rows, cols] of the block, as ``mash dist`` reports them (``shared/total`` in its output)."""
+        n = self.sizes()[0]
+        (r0, r1), (c0, c1) = _block_range(rows, n), _block_range(cols, n)
+        shape = (max(r1 - r0, 0), max(c1 - c0, 0))
+        shared = np.empty(shape, np.uint32)
+        total = np.empty(shape, np.uint32)
+        check(lib.sw_minhash_counts(self._h, c_u64(r0), c_u64(r1), c_u64(c0), c_u64(c1), _ptr(shared), _ptr(total)))
+        return shared, total
+
+    def jaccard(self, rows=None, cols=None) -> np.ndarray:
+        """float64[rows, cols]: ``shared / total`` as Python divides the two ints the reference parses (a pair of two empty
+        sketches raises ZeroDivisionError, as that division does)."""
+        shared, total = self.counts(rows, cols)
+        if np.any(total == 0):
+            raise ZeroDivisionError("division by zero")
+        return shared.astype(np.float64) / total.astype(np.float64)
+
+    def frac_rowsums(self, rows=None, cols=None) -> np.ndarray:
+        """Per row of the block: the sum of 2J / (1 + J) over its columns, added on the device in a fixed order."""
+        n = self.sizes()[0]
+        (r0, r1), (c0, c1) = _block_range(rows, n), _block_range(cols, n)
+        out = np.empty(max(r1 - r0, 0), np.float64)
+        try:
+            check(lib.sw_minhash_frac_rowsums(self._h, c_u64(r0), c_u64(r1), c_u64(c0), c_u64(c1), _ptr(out)))
+        except ValueError as e:
+            if "division by zero" in str(e):
+                raise ZeroDivisionError("division by zero") from None
+            raise
+        return out
+
+    def expected_frac(self, rows=None, cols=None) -> float:
+        """kmers._expected_frac (src/seqwin/kmers.py:315-323) of the block's Jaccard matrix: mean(2J / (1 + J)), without
+        materialising the matrix on the host."""
+        sums = self.frac_rowsums(rows, cols)
+        n = self.sizes()[0]
+        (r0, r1), (c0, c1) = _block_range(rows, n), _block_range(cols, n)
+        return float(np.float64(sums.sum()) / np.float64((r1 - r0) * (c1 - c0)))
+
+    def penalty_fracs(self, n_tar: int):
+        """(e_absence_tar, e_presence_neg) of kmers.filter_graph (src/seqwin/kmers.py:419-420); targets are the first ``n_tar``
+        assemblies."""
+        n = self.sizes()[0]
+        n_tar = int(n_tar)
+        if not 0 < n_tar < n:
+            raise ValueError(f"n_tar = {n_tar} must leave a target and a non-target among the {n} assemblies")
+        return 1 - self.expected_frac((0, n_tar), (0, n_tar)), self.expected_frac((n_tar, n), (0, n_tar))
+
+    def stats(self) -> dict:
+        c = (c_u64 * 4)()
+        ms = (ctypes.c_double * 2)()
+        check(lib.sw_minhash_stats(self._h, c, ms))
+        d = dict(zip(("general_route", "candidates", "largest_candidates", "capacity"), (int(x) for x in c)))
+        d.update(hash_ms=ms[0], select_ms=ms[1])
+        return d
+
+    def close(self) -> None:
+        if self._h:
+            lib.sw_minhash_free(self._h)
             self._h = None
 
     def __del__(self):
