@@ -364,6 +364,49 @@ int sw_markers_export_rows(const sw_markers *m, uint64_t *row_offsets, sw_marker
 int sw_markers_stats(const sw_markers *m, uint64_t *counters, double *ms);
 void sw_markers_free(sw_markers *m);
 
+/* ---- markers._fetch_cks_seq (src/seqwin/markers.py:428-471) and row edit distances on the device (csrc/seqs.hip) ---------------
+ * An interval is bases [start, stop) of record `record`, the batch's GLOBAL record index (record_offsets[assembly] + the record's
+ * index inside its assembly).  start <= stop <= the record's length, record below the batch's records: anything else is
+ * SW_ERR_VALUE naming the first such interval. */
+typedef struct sw_interval {
+    uint32_t record;
+    uint32_t start;
+    uint32_t stop;
+} sw_interval;
+#define SW_SEQ_INEXACT 1u /* the interval is not contained in one valid run: it holds a base that was no A, C, G, T (or U) in the file */
+typedef struct sw_seqs sw_seqs; /* opaque device-resident text of a list of intervals */
+/* Replaces Assemblies.fetch_seq / _fetch_seq (src/seqwin/assemblies.py:101-141, 282-297), which load every FASTA file again
+ * (utils.load_fasta, utils.py:492-530: the record text, upper-cased, sliced [start:stop]): the text of the intervals decoded from
+ * the resident packed bases -- A, C, G, T and N for every invalid base, as sw_batch_record writes them.  An interval without
+ * SW_SEQ_INEXACT is the reference's string (a U of the file reads as T). */
+int sw_batch_fetch(const sw_batch *b, const sw_interval *intervals, uint64_t n, sw_seqs **out);
+/* The same for the rows of a marker table -- markers._fetch_cks_seq, markers.py:428-471: rows == 0 the representatives, its
+ * rep_only; rows != 0 every row, which needs the rows kept -- of subgraphs select[0 .. n_select), in that order -- the intervals are
+ * made on the device.  SW_ERR_VALUE unless the batch's record table starts with the one the markers were located with. */
+int sw_markers_fetch(const sw_markers *m, const sw_batch *b, int rows, const uint64_t *select, uint64_t n_select, sw_seqs **out);
+/* Intervals and bytes of all their text (either may be NULL). */
+int sw_seqs_sizes(const sw_seqs *s, uint64_t *n, uint64_t *bytes);
+/* D2H copies (any pointer may be NULL): offsets[n + 1] into blob[bytes], flags[n] (SW_SEQ_INEXACT). */
+int sw_seqs_export(const sw_seqs *s, uint64_t *offsets, char *blob, uint8_t *flags);
+/* counters[2] = { launches of the decode kernel, bytes written }; ms[1] = { checks, offsets and decode } (HIP events). */
+int sw_seqs_stats(const sw_seqs *s, uint64_t *counters, double *ms);
+void sw_seqs_free(sw_seqs *s);
+/* No counterpart in the reference, which judges a candidate through BLAST alone (markers._eval_cks, markers.py:531-722); this is
+ * NOT BLAST and fills none of MarkerMetrics.  For n pairs of intervals (r[i], s[i]) of one batch, by DESIGN.md section 3.2c: the
+ * symbols are the four valid bases, an invalid base equals nothing (not even another invalid base) and its complement is invalid;
+ * d_fwd = the Levenshtein distance of R and S (substitution, insertion, deletion cost 1 each, both consumed whole), d_rev = that of
+ * R and the reverse complement of S; dist[i] = min(d_fwd, d_rev), strand[i] = 0 if d_fwd <= d_rev, else 1; a pair with an empty
+ * side has the other side's length and strand 0.  Exact for every pair.
+ * counters[6] (may be NULL) = { pairs, sum of |R| |S|, pairs done by the striped route (pattern above the block bound), longest
+ * side, kernel launches, the block bound }; ms[2] (may be NULL) = { checks + classes, distance kernels } (HIP events). */
+int sw_batch_edit_distances(const sw_batch *b, const sw_interval *r, const sw_interval *s, uint64_t n, uint32_t *dist, uint8_t *strand,
+                            uint64_t *counters, double *ms);
+/* The same with R = the representative of a subgraph and S = each of its rows (what markers._eval_cks, markers.py:531-722, asks
+ * BLAST about, answered for the located copies only): one entry per kept row of subgraphs select[0 .. n_select), in that order,
+ * the rows of a subgraph ascending by assembly.  Needs the rows kept; record table as for sw_markers_fetch. */
+int sw_markers_row_distances(const sw_markers *m, const sw_batch *b, const uint64_t *select, uint64_t n_select, uint32_t *dist,
+                             uint8_t *strand, uint64_t *counters, double *ms);
+
 /* ---- Assemblies.mash (src/seqwin/assemblies.py:76-99) on the device (csrc/minhash.hip) ---------------------------------------
  * MinHash sketches as `mash sketch -k K -s S` makes them, one per assembly, and the counts `mash dist` derives for a pair, by the
  * specification of DESIGN.md section 3 (Mash 2.x at its defaults; tests/tools/minhash_host.py restates it -- the `mash` binary

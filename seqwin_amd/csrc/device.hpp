@@ -203,6 +203,19 @@ struct sw_occ {   // ordered tuple stream of one shard (tuple-exchange form of t
     ~sw_occ();
 };
 
+struct sw_markers {   // markers.hip makes it; seqs.hip reads its rows as intervals of a batch
+    int device = 0;
+    int keep_rows = 0;
+    uint64_t n_sg = 0, n_rep_kmers = 0, n_rows = 0, n_row_kmers = 0;
+    sw::DevArray<sw_marker_rep> reps;
+    sw::DevArray<uint64_t> rep_off, rep_hashes;
+    sw::DevArray<uint64_t> row_off, kmer_off, row_hashes;
+    sw::DevArray<sw_marker_row> rows;
+    std::vector<uint32_t> record_offsets;   // [n_assemblies + 1] the record table the rows were located with (host)
+    uint64_t counters[4] = {};
+    double ms[4] = {};
+};
+
 namespace sw { struct EdgeHashJob; }
 struct sw_index {
     int device = 0;

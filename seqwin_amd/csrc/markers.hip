@@ -504,18 +504,6 @@ __global__ void k_rec_range(const sw_kmer *kmers, uint64_t n_kmers, const sw_nod
 }  // namespace
 }  // namespace sw
 
-struct sw_markers {
-    int device = 0;
-    int keep_rows = 0;
-    uint64_t n_sg = 0, n_rep_kmers = 0, n_rows = 0, n_row_kmers = 0;
-    sw::DevArray<sw_marker_rep> reps;
-    sw::DevArray<uint64_t> rep_off, rep_hashes;
-    sw::DevArray<uint64_t> row_off, kmer_off, row_hashes;
-    sw::DevArray<sw_marker_row> rows;
-    uint64_t counters[4] = {};
-    double ms[4] = {};
-};
-
 namespace sw {
 namespace {
 
@@ -642,6 +630,7 @@ void run_markers(const sw_kmer *kmers, uint64_t n_kmers, const sw_node *nodes, u
     o.n_sg = n_sg;
     o.n_rows = n_rows;
     o.keep_rows = keep_rows;
+    o.record_offsets.assign(ro_host, ro_host + n_asm + 1);
     if (keep_rows) {
         o.kmer_off.alloc(n_rows + 1);
         scan_exclusive(rocprim::make_transform_iterator(rocprim::make_counting_iterator<uint64_t>(0), RowLenAt{o.rows.p, n_rows}), o.kmer_off.p,

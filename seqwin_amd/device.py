@@ -121,6 +121,30 @@ class Batch:
                                    ctypes.byref(h)))
         return MinHash(h)
 
+    def fetch(self, intervals, stats: bool = False):
+        """The text of ``intervals`` (INTERVAL_DTYPE or an (n, 3) array of record, start, stop; ``record`` is the batch's global
+        record index), decoded from the resident packed bases (csrc/seqs.hip): ``(offsets, blob, inexact)`` -- interval i is
+        ``blob[offsets[i]:offsets[i + 1]]`` in A, C, G, T and N for every invalid base; ``inexact[i]`` says that it is not
+        contained in one valid run.  ValueError for an interval that does not lie inside its record."""
+        iv = _intervals(intervals)
+        h = c_vp()
+        check(lib.sw_batch_fetch(self._h, _ptr(iv), c_u64(len(iv)), ctypes.byref(h)))
+        return _export_seqs(h, stats)
+
+    def edit_distances(self, r, s, stats: bool = False):
+        """``(dist, strand)`` of the pairs of intervals ``(r[i], s[i])``: the smaller of the Levenshtein distances of R to S and to
+        the reverse complement of S, and which of the two it was (0 on a tie), by DESIGN.md section 3.2c (csrc/seqs.hip).  Not BLAST.
+        ``stats=True`` adds the call's counters and times as a third element."""
+        r, s = _intervals(r), _intervals(s)
+        if len(r) != len(s):
+            raise ValueError(f"{len(r)} intervals against {len(s)}")
+        dist = np.empty(len(r), np.uint32)
+        strand = np.empty(len(r), np.uint8)
+        c = (c_u64 * 6)()
+        ms = (ctypes.c_double * 2)()
+        check(lib.sw_batch_edit_distances(self._h, _ptr(r), _ptr(s), c_u64(len(r)), _ptr(dist), _ptr(strand), c, ms))
+        return (dist, strand, _distance_stats(c, ms)) if stats else (dist, strand)
+
     def close(self) -> None:
         if self._h:
             lib.sw_batch_free(self._h)
@@ -131,6 +155,46 @@ class Batch:
             self.close()
         except Exception:
             pass
+
+
+INTERVAL_DTYPE = np.dtype([("record", "<u4"), ("start", "<u4"), ("stop", "<u4")])
+SEQ_INEXACT = 1
+
+
+def _intervals(iv) -> np.ndarray:
+    a = np.asarray(iv)
+    if a.dtype != INTERVAL_DTYPE:
+        a = np.asarray(a, np.int64).reshape(-1, 3)
+        if a.size and (a.min() < 0 or a.max() > 0xFFFFFFFF):
+            raise ValueError("record, start and stop of an interval are 32-bit values")
+        out = np.empty(len(a), INTERVAL_DTYPE)
+        out["record"], out["start"], out["stop"] = a[:, 0], a[:, 1], a[:, 2]
+        a = out
+    return np.ascontiguousarray(a)
+
+
+def _export_seqs(h: c_vp, stats: bool = False):
+    """(offsets, blob, inexact) of a sw_seqs handle, which is freed; with ``stats`` the call's counters and time as a fourth."""
+    try:
+        n, nb = c_u64(), c_u64()
+        check(lib.sw_seqs_sizes(h, ctypes.byref(n), ctypes.byref(nb)))
+        offs = np.empty(n.value + 1, np.uint64)
+        blob = ctypes.create_string_buffer(max(nb.value, 1))
+        flags = np.empty(n.value, np.uint8)
+        check(lib.sw_seqs_export(h, _ptr(offs), blob, _ptr(flags)))
+        c = (c_u64 * 2)()
+        ms = (ctypes.c_double * 1)()
+        check(lib.sw_seqs_stats(h, c, ms))
+        out = (offs, blob.raw[:nb.value], (flags & SEQ_INEXACT).astype(bool))
+        return out + (dict(launches=int(c[0]), bytes=int(c[1]), ms=ms[0]),) if stats else out
+    finally:
+        lib.sw_seqs_free(h)
+
+
+def _distance_stats(c, ms) -> dict:
+    d = dict(zip(("pairs", "cells", "striped_pairs", "longest", "launches", "block_cap"), (int(x) for x in c)))
+    d.update(classify_ms=ms[0], distance_ms=ms[1])
+    return d
 
 
 class Index:
@@ -430,6 +494,39 @@ class Markers:
             a, b = ro[i], ro[i + 1]
             out.append((rows[a:b], (k_offs[a:b + 1] - k_offs[a]), hashes[ko[a]:ko[b]]))
         return out
+
+    def _selected(self, select) -> np.ndarray:
+        """Device (commit-order) indices of the subgraphs ``select`` names in the final order; None: all of them."""
+        sel = self.order if select is None else self.order[np.asarray(select, np.int64).reshape(-1)]
+        return np.ascontiguousarray(sel, np.uint64)
+
+    def sequences(self, batch: "Batch", which: str = "reps", select=None, stats: bool = False):
+        """``(offsets, blob, inexact)`` as :meth:`Batch.fetch` returns them, of the representative rows (``which="reps"``) or of
+        every row (``"rows"``, subgraph after subgraph, ascending by assembly: the concatenation of :meth:`rows`; needs
+        ``keep_rows=True``) of the subgraphs ``select`` (indices in the final order; None: all), in that order.  The intervals are
+        made on the device from the tables; a row's global record is ``batch.record_offsets()[assembly_idx] + record_idx``.
+        ValueError if the batch's record table does not cover the markers' records."""
+        if which not in ("reps", "rows"):
+            raise ValueError(f'which must be "reps" or "rows" (got {which!r})')
+        sel = self._selected(select)
+        h = c_vp()   # ("rows" without the rows kept: the library's ValueError, as rows() gives it)
+        check(lib.sw_markers_fetch(self._h, batch._h, ctypes.c_int(1 if which == "rows" else 0), _ptr(sel), c_u64(len(sel)), ctypes.byref(h)))
+        return _export_seqs(h, stats)
+
+    def row_distances(self, batch: "Batch", select=None, stats: bool = False):
+        """``(dist, strand)`` of :meth:`Batch.edit_distances` with R = the subgraph's representative interval and S = the row's, one
+        entry per kept row in the order of ``sequences(batch, "rows", select)``.  A representative's own row reads (0, 0) when it
+        holds no invalid base.  Needs ``keep_rows=True``; ValueError if the batch's record table does not cover the markers' records."""
+        sel = self._selected(select)
+        row_offs = np.empty(self.sizes()[0] + 1, np.uint64)
+        check(lib.sw_markers_export_rows(self._h, _ptr(row_offs), None, None, None))   # ValueError unless the rows were kept
+        n = int(np.diff(row_offs.astype(np.int64))[sel.astype(np.int64)].sum())
+        dist = np.empty(n, np.uint32)
+        strand = np.empty(n, np.uint8)
+        c = (c_u64 * 6)()
+        ms = (ctypes.c_double * 2)()
+        check(lib.sw_markers_row_distances(self._h, batch._h, _ptr(sel), c_u64(len(sel)), _ptr(dist), _ptr(strand), c, ms))
+        return (dist, strand, _distance_stats(c, ms)) if stats else (dist, strand)
 
     def candidates(self, min_len: int) -> np.ndarray:
         """Indices of the subgraphs the reference keeps (markers.py:514-517): len >= min_len, neither single nor dup."""

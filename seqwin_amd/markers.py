@@ -1,12 +1,17 @@
 """Drop-in for the per-subgraph step of Seqwin's markers._get_cks (src/seqwin/markers.py:474-528), on the device.
 
 ``get_cks`` takes the kept index and the subgraphs as they are resident after ``Index.filter_kmers(f, subgraphs)`` and returns the
-candidate markers as plain objects carrying the attributes that ``get_markers`` and ``_fetch_cks_seq`` read.  Not done here
-(DESIGN.md section 7): the graph ordering ``path`` (left ``None``), the sequence text (``rep['seq']`` is ``None``) and BLAST.
+candidate markers as plain objects carrying the attributes that ``get_markers`` and ``_fetch_cks_seq`` read.  Given the resident
+batch it also fills ``rep['seq']`` (``_fetch_cks_seq``, markers.py:428-471, without reading a file again), and ``save_markers``
+writes the two files ``get_markers`` ends with (markers.py:777-802).  ``row_summary`` condenses ``Markers.row_distances``.  Not
+done here: the graph ordering ``path`` (left ``None``) and BLAST.
 
 The attribute and field names are an interface, kept as data below and pinned by tests/test_gpu_markers.py.
 """
 from __future__ import annotations
+
+import gzip
+from pathlib import Path
 
 import numpy as np
 
@@ -61,13 +66,113 @@ def all_cks(markers: Markers, n_tar: int) -> list:
     return out
 
 
-def get_cks(kept: Index, subgraphs: Subgraphs, record_offsets, n_tar: int, kmerlen: int, windowsize: int, min_len: int) -> list:
-    """markers._get_cks up to the sequence fetch: the candidates with ``len >= min_len`` that are not bad, ``rep_ratio`` set."""
+def _load_records(path) -> list:
+    """The records of a FASTA file (``.gz``: gzip) the way utils.load_fasta (utils.py:492-530) yields them: the lines behind each
+    header joined, in upper case.  A file that does not start with '>' is a ValueError, as there."""
+    path = Path(path)
+    text = gzip.decompress(path.read_bytes()).decode() if path.suffix == ".gz" else path.read_text()
+    if text[:1] != ">":
+        raise ValueError(f"FASTA file must start with '>', in: {path}")
+    out = []
+    for record in text.split(">")[1:]:
+        eol = record.find("\n")
+        out.append("" if eol < 0 else record[eol:].replace("\n", "").upper())
+    return out
+
+
+def get_cks(kept: Index, subgraphs: Subgraphs, record_offsets, n_tar: int, kmerlen: int, windowsize: int, min_len: int,
+            batch=None, paths=None) -> list:
+    """markers._get_cks: the candidates with ``len >= min_len`` that are not bad, ``rep_ratio`` set.  With ``batch`` (the resident
+    batch the index was built from) ``rep['seq']`` is filled as ``str`` from the packed bases; a representative that holds a base
+    the batch does not keep (lower case aside: an N, an IUPAC letter) is read from ``paths[assembly_idx]`` the reference's way
+    instead, and is a ValueError naming the candidate when ``paths`` is not given.  Without a batch ``rep['seq']`` stays None."""
     m = kept.marker_locs(subgraphs, record_offsets, n_tar, kmerlen, windowsize)
     try:
-        cks = [ck for ck in all_cks(m, n_tar) if ck.len >= min_len and not ck.is_bad]
+        keep = [(i, ck) for i, ck in enumerate(all_cks(m, n_tar)) if ck.len >= min_len and not ck.is_bad]
+        cks = [ck for _, ck in keep]
+        if batch is not None and cks:
+            offs, blob, inexact = m.sequences(batch, "reps", select=[i for i, _ in keep])
+            bounds = offs.astype(np.int64).tolist()
+            loaded = {}   # assembly_idx -> its records: a file is read once however many flagged representatives lie in it
+            for j, ck in enumerate(cks):
+                rep = ck.rep
+                if not inexact[j]:
+                    rep["seq"] = blob[bounds[j]:bounds[j + 1]].decode("ascii")
+                elif paths is not None:
+                    a = rep["assembly_idx"]
+                    if a not in loaded:
+                        loaded[a] = _load_records(paths[a])
+                    rep["seq"] = loaded[a][int(rep["record_idx"])][int(rep["start"]):int(rep["stop"])]
+                else:
+                    raise ValueError(f"candidate {rep['assembly_idx']}-{int(rep['record_idx'])}-{int(rep['start'])}:{int(rep['stop'])} "
+                                     "holds a base that is not A, C, G or T: pass `paths` to read it from its file")
     finally:
         m.close()
     for ck in cks:
         ck.rep_ratio = ck.n_rep / n_tar
     return cks
+
+
+# WORKINGDIR.markers_fasta / .markers_csv (src/seqwin/config.py:276-277) and the fields of MarkerMetrics (markers.py:80-87)
+MARKERS_FASTA = "signatures.fasta"
+MARKERS_CSV = "signatures.csv"
+METRIC_NAMES = ("conservation f_tar_hits divergence f_neg_hits avg_repeats_tar avg_pident_tar avg_repeats_neg avg_pident_neg").split()
+
+
+def _file_to_write(path: Path, overwrite: bool) -> None:
+    if path.is_file():
+        if not overwrite:
+            raise FileExistsError(f"{path} exists (overwrite is off)")
+        path.unlink()
+    elif path.is_dir():
+        raise IsADirectoryError(f"Expected a file, but a directory is found: {path}")
+
+
+def save_markers(cks, record_ids, working_dir, overwrite: bool = False):
+    """The file-saving block of markers.get_markers (markers.py:777-802): ``signatures.fasta`` with one record per candidate under
+    the header ``{assembly_idx}-{record_id}-{start}:{stop}``, and ``signatures.csv`` with the header, the length, the metrics
+    (empty before any BLAST check), ``rep_ratio`` and the number of k-mers.  ``record_ids``: ids by assembly, as
+    ``Batch.records()`` returns them.  Returns the two paths."""
+    import pandas as pd
+    working_dir = Path(working_dir)
+    fasta_path, csv_path = working_dir / MARKERS_FASTA, working_dir / MARKERS_CSV
+    _file_to_write(fasta_path, overwrite)
+    fasta, rows = [], []
+    for ck in cks:
+        rep = ck.rep
+        header = f"{rep['assembly_idx']}-{record_ids[rep['assembly_idx']][rep['record_idx']]}-{rep['start']}:{rep['stop']}"
+        fasta.append(f">{header}\n{rep['seq']}\n")
+        rows.append((header, ck.len, *(getattr(ck.metrics, name) for name in METRIC_NAMES), ck.rep_ratio, rep["n_kmers"]))
+    fasta_path.write_text("".join(fasta), encoding="utf-8", newline="\n")
+    _file_to_write(csv_path, overwrite)
+    pd.DataFrame(rows, columns=("fasta_header", "length", *METRIC_NAMES, "rep_ratio", "n_nodes")).to_csv(
+        csv_path, index=False, encoding="utf-8", lineterminator="\n")
+    return fasta_path, csv_path
+
+
+ROW_SUMMARY_DTYPE = np.dtype([("identity_tar", "<f8"), ("f_tar_rows", "<f8"), ("distance_neg", "<f8"), ("f_neg_rows", "<f8")])
+
+
+def row_summary(markers: Markers, dist, n_tar: int, n_neg: int) -> np.ndarray:
+    """Per subgraph, from ``dist`` of ``markers.row_distances(batch)``: ``identity_tar`` = the sum over its target rows of
+    ``max(0, 1 - dist / len(R))`` divided by ``n_tar``, ``distance_neg`` = the sum over its other rows of ``min(1, dist / len(R))``
+    divided by ``n_neg``, and the rows of either kind over ``n_tar`` / ``n_neg`` (``f_tar_rows``, ``f_neg_rows``); R is the
+    subgraph's representative.  These are NOT BLAST's ``conservation`` / ``divergence``: only located copies count, by edit distance."""
+    reps = markers.reps()[0]
+    per = markers.rows()
+    out = np.zeros(len(per), ROW_SUMMARY_DTYPE)
+    dist = np.asarray(dist, np.float64)
+    if len(dist) != sum(len(r) for r, _, _ in per):
+        raise ValueError(f"{len(dist)} distances for {sum(len(r) for r, _, _ in per)} rows")
+    at = 0
+    for i, (rows, _, _) in enumerate(per):
+        d = dist[at:at + len(rows)]
+        at += len(rows)
+        length = np.float64(np.uint32(reps["stop"][i] - reps["start"][i]))
+        tar = rows["assembly_idx"] < n_tar
+        frac = d / length if length else np.ones(len(d))
+        out["identity_tar"][i] = np.maximum(0.0, 1.0 - frac[tar]).sum() / n_tar if n_tar else 0.0
+        out["f_tar_rows"][i] = tar.sum() / n_tar if n_tar else 0.0
+        out["distance_neg"][i] = np.minimum(1.0, frac[~tar]).sum() / n_neg if n_neg else 0.0
+        out["f_neg_rows"][i] = (~tar).sum() / n_neg if n_neg else 0.0
+    return out
