@@ -443,6 +443,37 @@ int sw_minhash_frac_rowsums(const sw_minhash *h, uint64_t r0, uint64_t r1, uint6
 int sw_minhash_stats(const sw_minhash *h, uint64_t *counters, double *ms);
 void sw_minhash_free(sw_minhash *h);
 
+/* ---- exact k-mer containment of query sequences in every assembly (csrc/screen.hip) ---------------------------------------------
+ * Stands where markers.eval_markers (src/seqwin/markers.py:607-696) BLASTs every representative against every assembly.  There is
+ * no counterpart in the reference: this is NOT BLAST and fills none of MarkerMetrics.  By DESIGN.md section 3.2d
+ * (tests/tools/screen_host.py restates it): the alphabet is ACGTU in either case, U reads as T, every other byte is invalid; a
+ * k-mer is a window of k valid bases inside one record and one valid run of the batch, or inside one query; its canonical form is
+ * the smaller of its 2k-bit word (A0 C1 G2 T3, first base most significant) and its reverse complement's.  counts[q][a] = how many
+ * of query q's DISTINCT canonical k-mers occur anywhere in assembly a -- multiplicity never counts, keys are the full words, nothing
+ * is hashed into a shorter identity and nothing is approximate. */
+typedef struct sw_screen sw_screen; /* opaque: the device-resident counts of one call */
+/* Query q is blob[offsets[q] .. offsets[q + 1]); offsets[0] = 0, non-decreasing.  k outside 1..32 (checked before a device is
+ * touched), a NULL handle, 2^32 - 256 or more bytes of query text, 2^31 or more distinct query k-mers -> SW_ERR_VALUE.  Zero
+ * queries give a 0 x n result.  The batch must be resident.  `stream` is a hipStream_t (0 = default stream); the call returns
+ * with the counts finished. */
+int sw_batch_screen(const sw_batch *batch, const uint64_t *offsets, const char *blob, uint64_t n_queries, uint64_t k, void *stream,
+                    sw_screen **out);
+/* Queries, assemblies, distinct canonical k-mers of all queries, k (any pointer may be NULL). */
+int sw_screen_sizes(const sw_screen *h, uint64_t *n_queries, uint64_t *n_assemblies, uint64_t *n_distinct, uint64_t *k);
+/* n_kmers[n_queries]: the distinct canonical k-mers of every query (0 for a query shorter than k or without a valid window). */
+int sw_screen_n_kmers(const sw_screen *h, uint32_t *n_kmers);
+/* Rows (queries) [r0, r1) x columns (assemblies) [c0, c1): counts of pair (r, c) at [(r - r0) * (c1 - c0) + (c - c0)] of the host
+ * array.  A range outside the result or r0 > r1 -> SW_ERR_VALUE. */
+int sw_screen_counts(const sw_screen *h, uint64_t r0, uint64_t r1, uint64_t c0, uint64_t c1, uint32_t *counts);
+/* counters[10] = { bytes of query text (query positions), valid query k-mers, distinct query k-mers, slots of the table, most slots
+ * a key visited at insertion, batch k-mers probed, hits (multiplicity counted), atomics issued into the bitmap, chunks of
+ * assemblies, launches of the probe kernel }; ms[3] = { query side with the table build, probe, reduce } (HIP events; probe and
+ * reduce summed over the chunks). */
+int sw_screen_stats(const sw_screen *h, uint64_t *counters, double *ms);
+/* probe_ms[chunks], reduce_ms[chunks] (either may be NULL): the two times of every chunk of assemblies, in order. */
+int sw_screen_chunk_ms(const sw_screen *h, double *probe_ms, double *reduce_ms);
+void sw_screen_free(sw_screen *h);
+
 /* ---- multi-GPU merge (one process per GPU; the exchange itself is done by the host side with
  *      torch.distributed / RCCL on the device buffers below).  Together these replace
  *      merge_thread_graphs (cpp/src/seqwin/build_internals.cpp:295-392) across GPUs. -------------- */

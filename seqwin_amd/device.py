@@ -121,6 +121,17 @@ class Batch:
                                    ctypes.byref(h)))
         return MinHash(h)
 
+    def screen(self, queries, kmerlen: int, stream: int = 0) -> "Screen":
+        """For every query (a list of ``str`` or ``bytes``) and every assembly: how many of the query's distinct canonical
+        ``kmerlen``-mers occur anywhere in the assembly, exactly (csrc/screen.hip).  ACGTU in either case, U
+        reads as T, every other byte ends a window.  Not BLAST.  ValueError for a k-mer length outside 1..32."""
+        qs = [q.encode("utf-8") if isinstance(q, str) else bytes(q) for q in queries]
+        offs = np.zeros(len(qs) + 1, np.uint64)
+        np.cumsum([len(q) for q in qs], out=offs[1:])
+        h = c_vp()
+        check(lib.sw_batch_screen(self._h, _ptr(offs), b"".join(qs), c_u64(len(qs)), c_u64(int(kmerlen)), c_vp(stream), ctypes.byref(h)))
+        return Screen(h)
+
     def fetch(self, intervals, stats: bool = False):
         """The text of ``intervals`` (INTERVAL_DTYPE or an (n, 3) array of record, start, stop; ``record`` is the batch's global
         record index), decoded from the resident packed bases (csrc/seqs.hip): ``(offsets, blob, inexact)`` -- interval i is
@@ -528,6 +539,14 @@ class Markers:
         check(lib.sw_markers_row_distances(self._h, batch._h, _ptr(sel), c_u64(len(sel)), _ptr(dist), _ptr(strand), c, ms))
         return (dist, strand, _distance_stats(c, ms)) if stats else (dist, strand)
 
+    def screen(self, batch: "Batch", kmerlen: int, select=None) -> "Screen":
+        """:meth:`Batch.screen` of the representatives' text -- ``sequences(batch, "reps", select)``, in that order -- against every
+        assembly of ``batch``.  A flagged (inexact) representative is screened as fetched: its ``N``s carry no k-mers.  ``kmerlen``
+        is the caller's choice; it need not be the graph's k."""
+        offs, blob, _ = self.sequences(batch, "reps", select)
+        o = offs.astype(np.int64)
+        return batch.screen([blob[o[i]:o[i + 1]] for i in range(len(o) - 1)], kmerlen)
+
     def candidates(self, min_len: int) -> np.ndarray:
         """Indices of the subgraphs the reference keeps (markers.py:514-517): len >= min_len, neither single nor dup."""
         reps = self.reps()[0]
@@ -665,6 +684,67 @@ class MinHash:
     def close(self) -> None:
         if self._h:
             lib.sw_minhash_free(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Screen:
+    """Exact k-mer containment counts of a list of queries in every assembly of a batch, resident on the device
+    (:meth:`Batch.screen`, :meth:`Markers.screen`; csrc/screen.hip).  It stands where ``eval_markers`` (src/seqwin/markers.py:607-696)
+    BLASTs the representatives, has no counterpart in the reference, is not BLAST and fills none of ``MarkerMetrics``.
+    ``rows`` (queries) / ``cols`` (assemblies) are None (all), a ``(lo, hi)`` pair, a slice or a range."""
+
+    def __init__(self, handle: c_vp):
+        self._h = handle
+
+    def sizes(self):
+        """(queries, assemblies, distinct canonical k-mers of all queries, k)"""
+        v = [c_u64() for _ in range(4)]
+        check(lib.sw_screen_sizes(self._h, *[ctypes.byref(x) for x in v]))
+        return tuple(x.value for x in v)
+
+    def n_kmers(self) -> np.ndarray:
+        """uint32[queries]: the distinct canonical k-mers of every query (0: shorter than k, or no valid window)."""
+        out = np.empty(self.sizes()[0], np.uint32)
+        check(lib.sw_screen_n_kmers(self._h, _ptr(out)))
+        return out
+
+    def counts(self, rows=None, cols=None) -> np.ndarray:
+        """uint32[rows, cols]: how many of the query's distinct canonical k-mers occur in the assembly."""
+        nq, na, _, _ = self.sizes()
+        (r0, r1), (c0, c1) = _block_range(rows, nq), _block_range(cols, na)
+        out = np.empty((max(r1 - r0, 0), max(c1 - c0, 0)), np.uint32)
+        check(lib.sw_screen_counts(self._h, c_u64(r0), c_u64(r1), c_u64(c0), c_u64(c1), _ptr(out)))
+        return out
+
+    def containment(self, rows=None, cols=None) -> np.ndarray:
+        """float64[rows, cols]: ``counts / n_kmers``; ``nan`` for a query without a k-mer."""
+        r0, r1 = _block_range(rows, self.sizes()[0])
+        nk = self.n_kmers()[r0:r1].astype(np.float64)
+        nk[nk == 0] = np.nan
+        return self.counts(rows, cols).astype(np.float64) / nk[:, None]
+
+    def stats(self) -> dict:
+        c = (c_u64 * 10)()
+        ms = (ctypes.c_double * 3)()
+        check(lib.sw_screen_stats(self._h, c, ms))
+        d = dict(zip(("query_positions", "query_kmers", "distinct_kmers", "table_capacity", "longest_chain", "batch_kmers", "hits", "atomics",
+                      "chunks", "launches"), (int(x) for x in c)))
+        probe = (ctypes.c_double * max(d["chunks"], 1))()
+        reduce_ = (ctypes.c_double * max(d["chunks"], 1))()
+        check(lib.sw_screen_chunk_ms(self._h, probe, reduce_))
+        d.update(table_ms=ms[0], probe_ms=ms[1], reduce_ms=ms[2], chunk_probe_ms=list(probe)[:d["chunks"]],
+                 chunk_reduce_ms=list(reduce_)[:d["chunks"]])
+        return d
+
+    def close(self) -> None:
+        if self._h:
+            lib.sw_screen_free(self._h)
             self._h = None
 
     def __del__(self):

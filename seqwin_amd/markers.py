@@ -176,3 +176,34 @@ def row_summary(markers: Markers, dist, n_tar: int, n_neg: int) -> np.ndarray:
         out["distance_neg"][i] = np.minimum(1.0, frac[~tar]).sum() / n_neg if n_neg else 0.0
         out["f_neg_rows"][i] = (~tar).sum() / n_neg if n_neg else 0.0
     return out
+
+
+SCREEN_SUMMARY_DTYPE = np.dtype([("n_kmers", "<u4"), ("containment_tar", "<f8"), ("f_tar", "<f8"), ("containment_neg", "<f8"), ("f_neg", "<f8")])
+
+
+def screen_summary(screen, n_tar: int, min_containment: float = 0.9) -> np.ndarray:
+    """Per query of a :class:`Screen` (or of a pair ``(counts, n_kmers)`` of host arrays), with the targets the first ``n_tar``
+    columns and the non-targets the rest: ``containment_tar`` / ``containment_neg`` = the mean over the group's assemblies of
+    ``counts / n_kmers``, ``f_tar`` / ``f_neg`` = the fraction of the group's assemblies with ``counts / n_kmers >= min_containment``,
+    all in float64.  A query without a k-mer, and an empty group, read ``nan``.  These are NOT BLAST's ``conservation`` /
+    ``divergence`` and none of ``MarkerMetrics``: shared exact k-mers say nothing about an alignment."""
+    counts, n_kmers = (screen.counts(), screen.n_kmers()) if hasattr(screen, "counts") else screen
+    counts = np.asarray(counts, np.uint32)
+    n_kmers = np.asarray(n_kmers, np.uint32)
+    if counts.ndim != 2 or n_kmers.shape != (counts.shape[0],):
+        raise ValueError(f"counts of shape {counts.shape} against {n_kmers.shape} k-mer counts")
+    n_tar = int(n_tar)
+    if not 0 <= n_tar <= counts.shape[1]:
+        raise ValueError(f"n_tar = {n_tar} lies outside the {counts.shape[1]} assemblies")
+    out = np.zeros(len(n_kmers), SCREEN_SUMMARY_DTYPE)
+    out["n_kmers"] = n_kmers
+    nk = n_kmers.astype(np.float64)
+    nk[nk == 0] = np.nan
+    c = counts.astype(np.float64) / nk[:, None]
+    for name, f_name, block in (("containment_tar", "f_tar", c[:, :n_tar]), ("containment_neg", "f_neg", c[:, n_tar:])):
+        if block.shape[1] == 0:
+            out[name] = out[f_name] = np.nan
+            continue
+        out[name] = block.sum(axis=1) / block.shape[1]
+        out[f_name] = np.where(np.isnan(nk), np.nan, (block >= np.float64(min_containment)).sum(axis=1) / block.shape[1])
+    return out
