@@ -474,6 +474,52 @@ int sw_screen_stats(const sw_screen *h, uint64_t *counters, double *ms);
 int sw_screen_chunk_ms(const sw_screen *h, double *probe_ms, double *reduce_ms);
 void sw_screen_free(sw_screen *h);
 
+/* ---- the best hit of every query in every assembly: seed vote + infix edit distance (csrc/hits.hip) ------------------------------
+ * Covers the ground of markers.eval_markers' output (src/seqwin/markers.py:531-604 keeps the best BLAST hit's nident, mismatch and
+ * gaps per (query, assembly)) with an exactly specified quantity of its own.  There is no counterpart in the reference: this is NOT
+ * BLAST, has no scores, no e-values and no local alignment, and fills none of MarkerMetrics.  DESIGN.md section 3.2e is the
+ * specification, tests/tools/hits_host.py restates it.  Queries, alphabet, k-mers and canonical words are those of the screen. */
+typedef struct sw_infix_pair {
+    uint32_t query;  /* index into the queries of the call */
+    uint32_t strand; /* 0: the query; 1: its reverse complement */
+    uint32_t record; /* the batch's global record index */
+    uint32_t start;
+    uint32_t stop;   /* the text: bases [start, stop) of the record */
+} sw_infix_pair;
+/* Layer A.  For n pairs: the pattern P is the query (strand 0) or its reverse complement (strand 1), the text T the interval; an
+ * invalid base equals nothing and its complement is invalid (section 3.2c).  With D[0][j] = 0, D[i][0] = i and the unit-cost
+ * Levenshtein recurrence: dist[i] = min over 0 <= j <= |T| of D[|P|][j] (the text's ends are free, the pattern is consumed whole),
+ * end[i] = start + the smallest j that attains it.  An empty query gives (0, start), an empty text (|P|, start).  Exact for every
+ * pair.  A pair that names no query, a strand above 1 or start > stop (checked before a handle or a device is touched), or an
+ * interval outside its record -> SW_ERR_VALUE.  counters[6] (may be NULL) = { pairs, sum of |P| |T|, pairs done by the striped
+ * route (query above the block bound), longest query, kernel launches, the block bound }; ms[1] (may be NULL) = { classes and
+ * distance kernels } (HIP events). */
+int sw_batch_infix_distances(const sw_batch *b, const uint64_t *offsets, const char *blob, uint64_t n_queries, const sw_infix_pair *pairs,
+                             uint64_t n, uint32_t *dist, uint32_t *end, uint64_t *counters, double *ms);
+typedef struct sw_hits sw_hits; /* opaque: the device-resident [n_queries][n_assemblies] results of one call */
+/* Layer B.  A canonical word is a seed iff exactly one valid window of ALL query text has it (both orientations are one word) and it
+ * is not its own reverse complement; every window of the batch whose canonical word is a seed is a hit (record r, position p,
+ * orientation o); hits vote for bands of 64 implied end positions, the winner of a (query, assembly) is the (r, o, b) with the
+ * largest c[b] + c[b + 1], ties to the smallest (r, o, b); Layer A on the winner's window gives dist and end.  A pair without a hit
+ * reads seeds = 0, record = end = dist = 0xFFFFFFFF, strand = 0.  k outside 1..32 (checked before a device is touched), a NULL
+ * handle, key fields that do not fit 64 bits -> SW_ERR_VALUE.  The batch must be resident; the call works on the default stream of
+ * the batch's device and returns with the results finished. */
+int sw_batch_best_hits(const sw_batch *batch, const uint64_t *offsets, const char *blob, uint64_t n_queries, uint64_t k, sw_hits **out);
+/* Queries, assemblies, seeds of all queries, k (any pointer may be NULL). */
+int sw_hits_sizes(const sw_hits *h, uint64_t *n_queries, uint64_t *n_assemblies, uint64_t *n_seeds, uint64_t *k);
+/* n_seeds[n_queries]: the seeds of every query. */
+int sw_hits_n_seeds(const sw_hits *h, uint32_t *n_seeds);
+/* Rows (queries) [r0, r1) x columns (assemblies) [c0, c1) of one field -- 0 seeds, 1 record, 2 strand, 3 end, 4 dist --: pair (r, c)
+ * at [(r - r0) * (c1 - c0) + (c - c0)] of the host array.  A range outside the result, r0 > r1 or another field -> SW_ERR_VALUE. */
+int sw_hits_block(const sw_hits *h, uint64_t field, uint64_t r0, uint64_t r1, uint64_t c0, uint64_t c1, uint32_t *out);
+/* counters[10] = { hits, seeds, chunks of assemblies, chunk splits, launches of the probe kernel, pairs aligned, pairs on the striped
+ * route, distinct query k-mers, keys the hit buffer held at the end, doublings of the buffer }; ms[4] = { query side, probe, sort +
+ * vote, distances } (HIP events, summed over the chunks). */
+int sw_hits_stats(const sw_hits *h, uint64_t *counters, double *ms);
+/* hits[chunks]: the hits of every chunk of assemblies, in order. */
+int sw_hits_chunk_hits(const sw_hits *h, uint64_t *hits);
+void sw_hits_free(sw_hits *h);
+
 /* ---- multi-GPU merge (one process per GPU; the exchange itself is done by the host side with
  *      torch.distributed / RCCL on the device buffers below).  Together these replace
  *      merge_thread_graphs (cpp/src/seqwin/build_internals.cpp:295-392) across GPUs. -------------- */

@@ -1,0 +1,857 @@
+// hits.hip -- the best hit of every query in every assembly of a resident batch: seed vote + infix edit distance.
+//
+// Stands where markers.eval_markers (src/seqwin/markers.py:607-696) BLASTs every representative against every assembly and keeps the
+// best hit's nident / mismatch / gaps of every (query, assembly) pair.  It has no counterpart in the reference, it is NOT BLAST and
+// it fills none of MarkerMetrics (DESIGN.md section 3.2e is the specification; tests/tools/hits_host.py restates it).
+//
+// Layer A, infix edit distance (sw_batch_infix_distances): the pattern is a query (or its reverse complement), the text an interval
+// of the batch; dist = min over the text's prefixes' ends of D[m][j] with a free start in the text, end = the first j of the minimum.
+//   k_ix_pack      the query text as 2-bit codes and a validity plane, both strands, once per call
+//   k_ix_classify  pairs with an empty side answered; the others listed by the power of two >= the query's blocks of 64 rows
+//   k_ix           ed_pair's recurrence (seqs.hip) with three differences: the pattern is always the query, the top row's horizontal
+//                  delta is 0, and the lane of the last block keeps the running minimum of the score and the first column that
+//                  attains it; one strand.  k_ix_striped: queries above the block bound, with the HBM carry row
+// Layer B, seed vote (sw_batch_best_hits): the query side is the screen's (screen_core.hpp); a canonical word that exactly one
+// valid window of all query text has, and that is not its own reverse complement, is a seed.
+//   k_hit_mult / k_hit_seeds   windows per distinct word; (query, offset, window-is-canonical) per seed
+//   k_hit_probe    k_scr_probe's run / tile / lane walk with its 16 grouped first-slot loads; a hit appends the 64-bit key
+//                  (query | record | orientation | band) to the hit buffer: one atomic on the cursor per wave
+//   per chunk of assemblies: the keys sorted over their used bits, run heads and lengths, k_hit_vote (score = run + next band's run,
+//   the winner of a (query, assembly) by atomicMax of (score, ~run index): the smallest key wins a tie), k_hit_finish (the winner's
+//   fields, its window as a pair of Layer A), and Layer A on the chunk's pairs.  A chunk whose hits overflow the buffer is redone in
+//   two halves; one assembly that overflows it has the buffer doubled.
+#include "screen_core.hpp"
+#include "seqs_core.hpp"
+
+namespace sw {
+namespace {
+
+constexpr hipStream_t HIT_STREAM = SQ_STREAM;
+constexpr uint32_t HIT_BAND_SHIFT = 6;                 // W = 64: part of the specification
+constexpr uint64_t HIT_BUFFER_BYTES = 1ull << 30;      // hit keys and the sort's second buffer together: speed only, no measurement behind it
+constexpr uint64_t HIT_MAX_KEYS = 1ull << 31;          // a run index and a score are 32-bit values
+constexpr uint32_t IX_CLASSES = 8;                     // group widths 1, 2, ... 64, then the striped route
+constexpr uint32_t IX_STRIPE_GROUPS = 1024;
+
+// workgroups per launch of the probe kernel; SEQWIN_AMD_HIT_MAX_BLOCKS (test library) lowers it
+uint32_t hit_launch_blocks()
+{
+    return (uint32_t)std::max<uint64_t>(std::min<uint64_t>(scr_env_u64(SW_TEST_GETENV("SEQWIN_AMD_HIT_MAX_BLOCKS"), SCR_MAX_BLOCKS), SCR_MAX_BLOCKS), 1);
+}
+
+uint32_t bits_of(uint64_t x)   // bits that hold 0 .. x
+{
+    uint32_t b = 0;
+    while (b < 64 && (x >> b)) ++b;
+    return b;
+}
+
+// ---- Layer A: the packed queries ------------------------------------------------------------------------------------------------
+// Strand s of the query text: base x of query q lies at index off[q] + x of stream s; stream 1 holds the reverse complements.
+// codes: 16 bases per word as the batch packs them; valid: a bit per base.
+__global__ __launch_bounds__(SCR_TPB) void k_ix_pack(uint64_t base, uint64_t end, const uint8_t *__restrict__ text, const uint64_t *__restrict__ off, uint32_t nq,
+                                                     uint64_t total, uint64_t groups, uint32_t *__restrict__ codes0, uint32_t *__restrict__ valid0,
+                                                     uint32_t *__restrict__ codes1, uint32_t *__restrict__ valid1)
+{
+    const uint64_t w = base + (uint64_t)blockIdx.x * SCR_TPB + threadIdx.x;   // (strand, group of 32 bases)
+    if (w >= end) return;
+    const bool rc = w >= groups;
+    const uint64_t grp = rc ? w - groups : w;
+    uint64_t g = grp * 32, c = 0;
+    uint32_t v = 0, q = query_of(off, nq, g);
+    for (uint32_t b = 0; b < 32 && g < total; ++b, ++g) {
+        while (g >= off[q + 1]) ++q;   // (g < off[nq]: empty queries are stepped over)
+        const uint64_t src = rc ? off[q + 1] - 1 - (g - off[q]) : g;
+        const uint64_t code = base_code(text[src]);
+        if (code < 4) {
+            c |= (rc ? 3 - code : code) << (2 * b);
+            v |= 1u << b;
+        }
+    }
+    uint32_t *codes = rc ? codes1 : codes0, *valid = rc ? valid1 : valid0;
+    codes[2 * grp] = (uint32_t)c;
+    codes[2 * grp + 1] = (uint32_t)(c >> 32);
+    valid[grp] = v;
+}
+
+struct QueryPack {
+    DevArray<uint32_t> codes[2], valid[2];
+    DevArray<uint64_t> off;   // [nq + 1]
+    uint64_t nq = 0;
+};
+
+void pack_queries(const uint8_t *d_text, const uint64_t *offsets, uint64_t nq, QueryPack &P)
+{
+    const uint64_t total = nq ? offsets[nq] : 0, groups = (total + 31) / 32;
+    P.nq = nq;
+    P.off.alloc(nq + 1);
+    if (nq) SW_HIP(hipMemcpyAsync(P.off.p, offsets, (nq + 1) * 8, hipMemcpyHostToDevice, HIT_STREAM));
+    for (int s = 0; s < 2; ++s) {
+        P.codes[s].alloc(2 * groups + 2);
+        P.valid[s].alloc(groups + 1);
+        SW_HIP(hipMemsetAsync(P.codes[s].p, 0, (2 * groups + 2) * 4, HIT_STREAM));
+        SW_HIP(hipMemsetAsync(P.valid[s].p, 0, (groups + 1) * 4, HIT_STREAM));
+    }
+    if (groups)
+        launch_1d(k_ix_pack, 2 * groups, HIT_STREAM, d_text, (const uint64_t *)P.off.p, (uint32_t)nq, total, groups, P.codes[0].p, P.valid[0].p, P.codes[1].p,
+                  P.valid[1].p);
+}
+
+// bit i set: base g + i of the stream is valid, i < cnt <= 32 (the plane has a word behind its last)
+__device__ __forceinline__ uint32_t plane32(const uint32_t *__restrict__ valid, uint64_t g, uint32_t cnt)
+{
+    const uint64_t w = g >> 5;
+    const uint32_t sh = (uint32_t)(g & 31);
+    uint64_t x = valid[w];
+    if (sh + cnt > 32) x |= (uint64_t)valid[w + 1] << 32;
+    x >>= sh;
+    return (uint32_t)x & (cnt >= 32 ? 0xFFFFFFFFu : (1u << cnt) - 1);
+}
+
+// ---- Layer A: the kernels -------------------------------------------------------------------------------------------------------
+struct IxArgs {
+    RunTable t;
+    const uint32_t *codes[2], *valid[2];
+    const uint64_t *qoff;
+    const sw_infix_pair *pairs;
+    const uint32_t *out_idx;   // where pair i's results go (nullptr: i)
+    const uint32_t *list;      // pair indices of this launch's class
+    uint64_t count;
+    uint32_t g;                // lanes per pair (a power of two <= 64)
+    uint8_t *carry;            // striped route: one row of carry_stride bytes per group of the launch
+    uint64_t carry_stride;     // a multiple of 8, >= the longest text + 8
+    uint32_t *dist, *end;
+};
+
+// The group's lanes call this together.  Pattern: strand p.strand of query p.query, m >= 1 bases; text: [p.start, p.stop), n >= 1.
+__device__ void infix_pair(const IxArgs &a, const sw_infix_pair &p, uint32_t g, uint32_t b, uint8_t *carry, uint32_t *dist_out, uint32_t *end_out)
+{
+    const RunTable &t = a.t;
+    const uint64_t qbase = a.qoff[p.query];
+    const uint32_t m = (uint32_t)(a.qoff[p.query + 1] - qbase), n = p.stop - p.start;
+    const uint32_t *codes = a.codes[p.strand & 1u], *valid = a.valid[p.strand & 1u];
+    const uint32_t nb = (m + 63) >> 6, n_stripes = (nb + g - 1) / g;
+    const uint64_t tbase = t.rec_base[p.record] + p.start;
+    uint32_t score = m, best = m, best_col = 0;   // column 0 of the table: no text consumed, D[m][0] = m
+    RunMemo tm;
+    for (uint32_t s = 0; s < n_stripes; ++s) {
+        const uint32_t B = s * g + b, sb = nb - s * g < g ? nb - s * g : g;
+        const bool active = b < sb, last_block = B == nb - 1, first = s == 0;
+        const bool leaves_carry = active && b == sb - 1 && !last_block;
+        uint64_t lo = 0, hi = 0, vm = 0;   // the block's rows as bit planes: low and high bit of the code, validity
+        if (active) {
+            const uint32_t pos = 64 * B, cnt = m - pos < 64 ? m - pos : 64, c0 = cnt < 32 ? cnt : 32, c1 = cnt - c0;
+            const uint64_t x0 = load_codes(codes, qbase + pos, c0);
+            vm = plane32(valid, qbase + pos, c0);
+            lo = even_bits(x0);
+            hi = even_bits(x0 >> 1);
+            if (c1) {
+                const uint64_t x1 = load_codes(codes, qbase + pos + 32, c1);
+                vm |= (uint64_t)plane32(valid, qbase + pos + 32, c1) << 32;
+                lo |= (uint64_t)even_bits(x1) << 32;
+                hi |= (uint64_t)even_bits(x1 >> 1) << 32;
+            }
+        }
+        const uint32_t out_bit = last_block ? (m - 1) & 63u : 63u;
+        uint64_t Pv = ~0ull, Mv = 0;
+        uint64_t tf = 0, cbuf = 0;   // lane 0: 32 columns of the text, 8 columns of the carry row
+        uint32_t vf = 0;
+        uint32_t msg = 0;            // column base [0,3) and delta [3,5)
+        const uint32_t steps = n + sb - 1;
+        for (uint32_t step = 0; step < steps; ++step) {
+            uint32_t in = __shfl_up(msg, 1, g);
+            if (b == 0 && step < n) {
+                const uint32_t i = step & 31u;
+                if (i == 0) {
+                    const uint32_t cnt = n - step < 32 ? n - step : 32;
+                    tf = load_codes(t.packed, tbase + step, cnt);
+                    vf = valid32(t, p.record, p.start + step, cnt, tm);
+                }
+                const uint32_t cf = ((vf >> i) & 1u) ? (uint32_t)(tf >> (2 * i)) & 3u : 4u;
+                uint32_t hf = 0;   // the top row of the table is 0 in every column: the match may start anywhere in the text
+                if (!first) {
+                    if ((step & 7u) == 0) cbuf = *reinterpret_cast<const uint64_t *>(carry + step);
+                    hf = (uint32_t)(cbuf >> (8 * (step & 7u))) & 3u;
+                }
+                in = cf | (hf << 3);
+            }
+            const uint32_t col = step - b;   // (wraps below zero: then >= n)
+            if (active && step >= b && col < n) {
+                const uint32_t cf = in & 7u, hf = (in >> 3) & 3u;
+                const uint64_t ef = cf < 4 ? ~(lo ^ (0ull - (cf & 1u))) & ~(hi ^ (0ull - ((cf >> 1) & 1u))) & vm : 0ull;
+                const uint32_t of = myers_step(ef, Pv, Mv, hf, out_bit);
+                if (last_block) {
+                    score += of == 1 ? 1u : of == 2 ? 0xFFFFFFFFu : 0u;
+                    if (score < best) {   // (strictly: the first column that attains the minimum stays)
+                        best = score;
+                        best_col = col + 1;
+                    }
+                } else if (leaves_carry) {
+                    carry[col] = (uint8_t)of;   // (read by lane 0 of the next stripe, which is past this column there)
+                }
+                msg = cf | (of << 3);
+            }
+        }
+        if (n_stripes > 1) __threadfence();   // the row is complete and visible before the next stripe reads it
+        if (active && last_block) {
+            *dist_out = best;
+            *end_out = p.start + best_col;
+        }
+    }
+}
+
+// register route: group x of the launch does pair list[x]
+__global__ __launch_bounds__(SQ_TPB) void k_ix(IxArgs a)
+{
+    const uint64_t tid = (uint64_t)blockIdx.x * SQ_TPB + threadIdx.x, grp = tid / a.g;
+    if (grp >= a.count) return;   // (whole groups)
+    const uint32_t i = a.list[grp], oi = a.out_idx ? a.out_idx[i] : i;
+    infix_pair(a, a.pairs[i], a.g, (uint32_t)(tid % a.g), nullptr, a.dist + oi, a.end + oi);
+}
+
+// striped route: group x of the launch does pairs list[x], list[x + groups], ... with row x of the scratch
+__global__ __launch_bounds__(SQ_TPB) void k_ix_striped(IxArgs a, uint32_t groups)
+{
+    const uint64_t tid = (uint64_t)blockIdx.x * SQ_TPB + threadIdx.x, grp = tid / a.g;
+    if (grp >= groups) return;
+    for (uint64_t x = grp; x < a.count; x += groups) {
+        const uint32_t i = a.list[x], oi = a.out_idx ? a.out_idx[i] : i;
+        infix_pair(a, a.pairs[i], a.g, (uint32_t)(tid % a.g), a.carry + grp * a.carry_stride, a.dist + oi, a.end + oi);
+        __threadfence();   // (the row is reused by the group's next pair)
+    }
+}
+
+// A pair with an empty side is answered here; every other one is appended to the list of its class.
+// stat[0 .. 7]: entries of the class lists, [8] sum of |query| |text|, [9] longest query, [10] longest text of the striped class
+__global__ __launch_bounds__(SQ_TPB) void k_ix_classify(const sw_infix_pair *__restrict__ pairs, const uint32_t *__restrict__ out_idx, const uint64_t *__restrict__ qoff,
+                                                        uint64_t n, uint32_t cap, uint32_t *__restrict__ lists, unsigned long long *__restrict__ stat,
+                                                        uint32_t *__restrict__ dist, uint32_t *__restrict__ end)
+{
+    const uint64_t i = (uint64_t)blockIdx.x * SQ_TPB + threadIdx.x;
+    const uint32_t lane = threadIdx.x % SQ_WAVE;
+    uint32_t cls = IX_CLASSES, m = 0, tn = 0;
+    unsigned long long cells = 0;
+    if (i < n) {
+        const sw_infix_pair p = pairs[i];
+        m = (uint32_t)(qoff[p.query + 1] - qoff[p.query]);
+        tn = p.stop - p.start;
+        cells = (unsigned long long)m * tn;
+        if (m == 0 || tn == 0) {
+            const uint32_t oi = out_idx ? out_idx[i] : (uint32_t)i;
+            dist[oi] = m;         // an empty query: 0; an empty text: the whole query is inserted
+            end[oi] = p.start;
+        } else {
+            const uint32_t nb = (m + 63) >> 6;
+            cls = 0;
+            if (nb > cap) cls = IX_CLASSES - 1;
+            else
+                while ((1u << cls) < nb) ++cls;
+        }
+    }
+    for (uint32_t c = 0; c < IX_CLASSES; ++c) {
+        const unsigned long long mask = __ballot(cls == c);
+        if (!mask) continue;   // (uniform)
+        unsigned long long at = 0;
+        if (lane == (uint32_t)__ffsll((long long)mask) - 1) at = atomicAdd(stat + c, (unsigned long long)__popcll(mask));
+        at = __shfl(at, __ffsll((long long)mask) - 1, SQ_WAVE);
+        if (cls == c) lists[(uint64_t)c * n + at + __popcll(mask & ((1ull << lane) - 1))] = (uint32_t)i;
+    }
+    for (uint32_t d = SQ_WAVE / 2; d; d >>= 1) cells += __shfl_down(cells, d, SQ_WAVE);
+    if (lane == 0 && cells) atomicAdd(stat + 8, cells);
+    if (m) atomicMax(stat + 9, (unsigned long long)m);
+    if (cls == IX_CLASSES - 1) atomicMax(stat + 10, (unsigned long long)tn);
+}
+
+// dist / end of n valid pairs (device list).  counters[6] = { pairs, cells, striped pairs, longest query, launches, block bound }
+void infix_device(const RunTable &t, const QueryPack &P, const sw_infix_pair *d_pairs, const uint32_t *d_out_idx, uint64_t n, uint32_t *d_dist, uint32_t *d_end,
+                  uint64_t *counters, double *ms_out)
+{
+    Event e0, e1;
+    SW_HIP(hipEventRecord(e0, HIT_STREAM));
+    const uint32_t cap = ed_cap_blocks();
+    unsigned long long stat[11] = {};
+    uint64_t launches = 0;
+    if (n) {
+        if (n > SQ_MAX_LIST) raise(SW_ERR_VALUE, "infix distances: %llu pairs exceed one launch of the list kernels (%llu)", (unsigned long long)n, (unsigned long long)SQ_MAX_LIST);
+        DevArray<uint32_t> lists((uint64_t)IX_CLASSES * n);
+        DevArray<unsigned long long> d_stat(11);
+        SW_HIP(hipMemsetAsync(d_stat.p, 0, sizeof stat, HIT_STREAM));
+        hipLaunchKernelGGL(k_ix_classify, dim3(sq_blocks(n)), dim3(SQ_TPB), 0, HIT_STREAM, d_pairs, d_out_idx, (const uint64_t *)P.off.p, n, cap, lists.p, d_stat.p,
+                           d_dist, d_end);
+        SW_HIP(hipGetLastError());
+        SW_HIP(hipMemcpyAsync(stat, d_stat.p, sizeof stat, hipMemcpyDeviceToHost, HIT_STREAM));
+        SW_HIP(hipStreamSynchronize(HIT_STREAM));
+        IxArgs a{};
+        a.t = t;
+        for (int s = 0; s < 2; ++s) {
+            a.codes[s] = P.codes[s].p;
+            a.valid[s] = P.valid[s].p;
+        }
+        a.qoff = P.off.p;
+        a.pairs = d_pairs;
+        a.out_idx = d_out_idx;
+        a.dist = d_dist;
+        a.end = d_end;
+        const uint64_t max_threads = (uint64_t)sq_launch_blocks() * SQ_TPB;
+        for (uint32_t c = 0; c + 1 < IX_CLASSES; ++c) {   // register route, g = 2^c lanes per pair
+            const uint64_t cnt = stat[c], g = 1ull << c, per_launch = std::max<uint64_t>(max_threads / g, 1);
+            for (uint64_t x0 = 0; x0 < cnt; x0 += per_launch, ++launches) {
+                a.list = lists.p + (uint64_t)c * n + x0;
+                a.count = std::min<uint64_t>(per_launch, cnt - x0);
+                a.g = (uint32_t)g;
+                hipLaunchKernelGGL(k_ix, dim3(sq_blocks(a.count * g)), dim3(SQ_TPB), 0, HIT_STREAM, a);
+                SW_HIP(hipGetLastError());
+            }
+        }
+        DevArray<uint8_t> scratch;
+        if (const uint64_t cnt = stat[IX_CLASSES - 1]) {   // striped route: the largest power of two <= cap lanes per pair
+            uint32_t g = 1;
+            while (g * 2 <= cap) g *= 2;
+            const uint32_t groups = (uint32_t)std::min<uint64_t>({cnt, (uint64_t)IX_STRIPE_GROUPS, std::max<uint64_t>(max_threads / g, 1)});
+            a.carry_stride = ((uint64_t)stat[10] + 15) & ~7ull;
+            scratch.alloc((uint64_t)groups * a.carry_stride);
+            a.carry = scratch.p;
+            a.list = lists.p + (uint64_t)(IX_CLASSES - 1) * n;
+            a.count = cnt;
+            a.g = g;
+            hipLaunchKernelGGL(k_ix_striped, dim3(sq_blocks((uint64_t)groups * g)), dim3(SQ_TPB), 0, HIT_STREAM, a, groups);
+            SW_HIP(hipGetLastError());
+            ++launches;
+        }
+        SW_HIP(hipEventRecord(e1, HIT_STREAM));
+        SW_HIP(hipStreamSynchronize(HIT_STREAM));   // (lists / scratch go back to the pool behind the kernels)
+    } else {
+        SW_HIP(hipEventRecord(e1, HIT_STREAM));
+        SW_HIP(hipStreamSynchronize(HIT_STREAM));
+    }
+    if (counters) {
+        const uint64_t cn[6] = {n, stat[8], stat[IX_CLASSES - 1], stat[9], launches, cap};
+        memcpy(counters, cn, sizeof cn);
+    }
+    if (ms_out) {
+        float ms = 0;
+        SW_HIP(hipEventElapsedTime(&ms, e0, e1));
+        ms_out[0] = ms;
+    }
+}
+
+// ---- Layer B: seeds -------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(SCR_TPB) void k_hit_mult(uint64_t base, uint64_t end, const uint32_t *__restrict__ sidx, const uint32_t *__restrict__ number,
+                                                      uint32_t *__restrict__ mult)
+{
+    const uint64_t j = base + (uint64_t)blockIdx.x * SCR_TPB + threadIdx.x;
+    if (j < end) atomicAdd(mult + number[sidx[j]], 1u);
+}
+
+// valid window j whose word no other window has and that is not its own reverse complement: the seed of its word's number
+__global__ __launch_bounds__(SCR_TPB) void k_hit_seeds(uint64_t base, uint64_t end, const uint32_t *__restrict__ sidx, const uint32_t *__restrict__ number,
+                                                       const uint32_t *__restrict__ mult, const uint64_t *__restrict__ by_number, const uint32_t *__restrict__ vpos,
+                                                       const uint8_t *__restrict__ text, const uint64_t *__restrict__ off, uint32_t nq, uint32_t k,
+                                                       uint32_t *__restrict__ seed_q, uint32_t *__restrict__ seed_i, uint8_t *__restrict__ seed_fc,
+                                                       uint32_t *__restrict__ n_seeds)
+{
+    const uint64_t j = base + (uint64_t)blockIdx.x * SCR_TPB + threadIdx.x;
+    if (j >= end) return;
+    const uint32_t id = number[sidx[j]];
+    if (mult[id] != 1) return;
+    const uint64_t word = by_number[id];
+    uint64_t rc = 0, x = word, fwd = 0;
+    const uint64_t pos = vpos[j];
+    for (uint32_t i = 0; i < k; ++i) {
+        rc = (rc << 2) | (3 - (x & 3));
+        x >>= 2;
+        fwd = (fwd << 2) | (uint64_t)(base_code(text[pos + i]) & 3u);
+    }
+    if (rc == word) return;   // its own reverse complement: the orientation of a hit would be undefined
+    const uint32_t q = query_of(off, nq, pos);
+    seed_q[id] = q;
+    seed_i[id] = (uint32_t)(pos - off[q]);
+    seed_fc[id] = fwd == word ? 1 : 0;
+    atomicAdd(n_seeds + q, 1u);
+}
+
+// ---- Layer B: probe -------------------------------------------------------------------------------------------------------------
+struct HitArgs {
+    const uint32_t *packed;
+    const uint64_t *run_base;
+    const uint32_t *run_nk, *run_tile_off, *run_rec, *run_pos;
+    uint32_t n_runs, tile_begin, tile_end;
+    Table t;
+    const uint32_t *seed_q, *seed_i;
+    const uint8_t *seed_fc;
+    const uint64_t *qoff;
+    uint64_t *buf;
+    uint64_t cap;                    // keys the buffer holds
+    unsigned long long *cursor;      // keys appended (above cap: the chunk overflowed and nothing more is written)
+    uint32_t k, band_bits, rec_bits;
+};
+
+__global__ __launch_bounds__(SCR_TPB) void k_hit_probe(HitArgs g)
+{
+    const uint32_t wave = threadIdx.x / SCR_WAVE, lane = threadIdx.x % SCR_WAVE;
+    const uint64_t tile64 = (uint64_t)g.tile_begin + (uint64_t)blockIdx.x * SCR_WPB + wave;
+    if (tile64 >= g.tile_end) return;   // (the whole wave)
+    if (*(volatile unsigned long long *)g.cursor > g.cap) return;   // (the whole wave: the chunk has overflowed, it is redone anyway)
+    const uint32_t tile = (uint32_t)tile64;
+    uint32_t lo = 0, hi = g.n_runs;     // the last run whose first tile is <= tile
+    while (lo + 1 < hi) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (g.run_tile_off[mid] <= tile) lo = mid; else hi = mid;
+    }
+    const uint32_t r = lo, nk = g.run_nk[r];
+    const uint64_t first = (uint64_t)(tile - g.run_tile_off[r]) * SCR_TILE + (uint64_t)lane * SCR_L;
+    const uint32_t n_mine = first < nk ? (uint32_t)(nk - first < SCR_L ? nk - first : SCR_L) : 0;
+    const uint32_t k = g.k;
+    const uint64_t mask = k >= 32 ? ~0ull : (1ull << (2 * k)) - 1;
+    const uint32_t sh = 2 * (k - 1);
+    uint64_t key[SCR_L];
+    uint32_t have = 0, cnt = 0;         // bit j: key[j] is a hit
+    if (n_mine) {
+        uint64_t pos = g.run_base[r] + first, fwd = 0, rev = 0;
+        uint32_t w = g.packed[pos >> 4] >> (2 * (uint32_t)(pos & 15)), left = 16 - (uint32_t)(pos & 15);
+        auto roll = [&]() {
+            if (left == 0) {
+                w = g.packed[pos >> 4];
+                left = 16;
+            }
+            const uint64_t c = w & 3u;
+            w >>= 2;
+            --left;
+            ++pos;
+            fwd = ((fwd << 2) | c) & mask;
+            rev = (rev >> 2) | ((3 - c) << sh);
+        };
+        for (uint32_t i = 0; i + 1 < k; ++i) roll();
+        uint64_t canon[SCR_L];
+        uint32_t home[SCR_L], slot[SCR_L], is_fwd = 0;
+#pragma unroll
+        for (uint32_t j = 0; j < SCR_L; ++j) {
+            canon[j] = 0;
+            if (j < n_mine) {
+                roll();
+                canon[j] = fwd < rev ? fwd : rev;
+                is_fwd |= (fwd < rev ? 1u : 0u) << j;
+            }
+        }
+#pragma unroll
+        for (uint32_t j = 0; j < SCR_L; ++j) {   // the 16 first-slot loads leave together
+            home[j] = scr_home(canon[j], g.t.bits);
+            slot[j] = j < n_mine ? g.t.slots[home[j]] : 0u;
+        }
+        const uint32_t rec = g.run_rec[r];
+        const uint64_t p0 = (uint64_t)g.run_pos[r] + first;
+#pragma unroll
+        for (uint32_t j = 0; j < SCR_L; ++j) {
+            key[j] = 0;
+            if (!slot[j]) continue;
+            const uint32_t id = scr_find_from(g.t, canon[j], home[j], slot[j]);
+            if (id == SCR_NONE) continue;
+            const uint32_t q = g.seed_q[id];
+            if (q == SCR_NONE) continue;
+            const uint64_t m = g.qoff[q + 1] - g.qoff[q], i = g.seed_i[id];
+            const uint32_t o = (((is_fwd >> j) & 1u) != (uint32_t)g.seed_fc[id]) ? 1u : 0u;
+            const uint64_t io = o ? m - k - i : i, e = p0 + j + (m - k) - io;   // (m - k - io >= 0)
+            key[j] = ((((uint64_t)q << g.rec_bits | rec) << 1 | o) << g.band_bits) | (e >> HIT_BAND_SHIFT);
+            have |= 1u << j;
+            ++cnt;
+        }
+    }
+    // one atomic on the cursor per wave: the lanes' counts scanned, the wave's range claimed by lane 0
+    uint32_t incl = cnt;
+    for (uint32_t d = 1; d < SCR_WAVE; d <<= 1) {
+        const uint32_t o = __shfl_up(incl, d, SCR_WAVE);
+        if (lane >= d) incl += o;
+    }
+    const uint32_t total = __shfl(incl, SCR_WAVE - 1, SCR_WAVE);
+    if (!total) return;   // (uniform)
+    unsigned long long at = 0;
+    if (lane == 0) at = atomicAdd(g.cursor, (unsigned long long)total);
+    at = __shfl(at, 0, SCR_WAVE);
+    if (at + total > g.cap) return;   // (uniform) overflow: the host reads it from the cursor
+    at += incl - cnt;
+#pragma unroll
+    for (uint32_t j = 0; j < SCR_L; ++j)
+        if ((have >> j) & 1u) g.buf[at++] = key[j];
+}
+
+// ---- Layer B: vote --------------------------------------------------------------------------------------------------------------
+// run r of the sorted keys: score = its length + the length of the run of the next band, if that is the next run.  The winner of a
+// (query, assembly): the largest (score, ~r) -- the runs ascend by (record, orientation, band) inside the pair
+__global__ __launch_bounds__(SCR_TPB) void k_hit_vote(uint64_t base, uint64_t end, const uint64_t *__restrict__ ukey, const uint32_t *__restrict__ upos, uint64_t n_keys,
+                                                      const uint32_t *__restrict__ rec_asm, uint32_t band_bits, uint32_t rec_bits, uint32_t asm0, uint32_t rows,
+                                                      unsigned long long *__restrict__ best)
+{
+    const uint64_t r = base + (uint64_t)blockIdx.x * SCR_TPB + threadIdx.x;
+    if (r >= end) return;
+    const uint64_t n_runs = end, key = ukey[r];   // (launched over all runs in one range or several: `end` of the last is n_runs)
+    const uint64_t next = r + 1 < n_runs ? upos[r + 1] : n_keys;
+    uint64_t score = next - upos[r];
+    if (r + 1 < n_runs && ukey[r + 1] == key + 1) score += (r + 2 < n_runs ? upos[r + 2] : n_keys) - next;
+    const uint32_t rec = (uint32_t)((key >> (band_bits + 1)) & ((1ull << rec_bits) - 1));
+    const uint64_t q = key >> (band_bits + 1 + rec_bits);
+    atomicMax(best + q * rows + (rec_asm[rec] - asm0), (unsigned long long)(score << 32 | (0xFFFFFFFFull - r)));
+}
+
+// cell (query, assembly of the chunk) with a winner: its fields, and its window as a pair of Layer A
+__global__ __launch_bounds__(SCR_TPB) void k_hit_finish(uint64_t base, uint64_t end, const unsigned long long *__restrict__ best, const uint64_t *__restrict__ ukey,
+                                                        const uint64_t *__restrict__ qoff, const uint32_t *__restrict__ rec_len, uint32_t k, uint32_t band_bits,
+                                                        uint32_t rec_bits, uint32_t asm0, uint32_t rows, uint64_t n_asm, uint32_t *__restrict__ seeds,
+                                                        uint32_t *__restrict__ record, uint32_t *__restrict__ strand, sw_infix_pair *__restrict__ pairs,
+                                                        uint32_t *__restrict__ out_idx, uint32_t *__restrict__ n_pairs)
+{
+    const uint64_t c = base + (uint64_t)blockIdx.x * SCR_TPB + threadIdx.x;
+    if (c >= end) return;
+    const unsigned long long v = best[c];
+    if (!v) return;
+    const uint64_t q = c / rows, a = asm0 + c % rows, cell = q * n_asm + a;
+    const uint64_t key = ukey[0xFFFFFFFFull - (v & 0xFFFFFFFFull)];
+    const uint64_t band = key & ((1ull << band_bits) - 1);
+    const uint32_t o = (uint32_t)(key >> band_bits) & 1u, rec = (uint32_t)((key >> (band_bits + 1)) & ((1ull << rec_bits) - 1));
+    seeds[cell] = (uint32_t)(v >> 32);
+    record[cell] = rec;
+    strand[cell] = o;
+    const long long m = (long long)(qoff[q + 1] - qoff[q]), s0 = (long long)(band << HIT_BAND_SHIFT) - (m - (long long)k);
+    const long long lo = s0 - 64 > 0 ? s0 - 64 : 0, len = rec_len[rec], hi = s0 + 192 + m < len ? s0 + 192 + m : len;
+    const uint32_t at = atomicAdd(n_pairs, 1u);
+    pairs[at] = sw_infix_pair{(uint32_t)q, o, rec, (uint32_t)lo, (uint32_t)hi};
+    out_idx[at] = (uint32_t)cell;
+}
+
+}  // namespace
+}  // namespace sw
+
+struct sw_hits {
+    int device = 0;
+    uint64_t nq = 0, n_asm = 0, k = 0, n_seeds_total = 0;
+    std::vector<uint32_t> n_seeds;                 // [nq]
+    sw::DevArray<uint32_t> field[5];               // [nq][n_asm] seeds, record, strand, end, dist
+    uint64_t counters[10] = {};
+    double ms[4] = {};
+    std::vector<uint64_t> chunk_hits;
+};
+
+namespace sw {
+namespace {
+
+void check_queries(const char *what, const uint64_t *offsets, const char *blob, uint64_t nq)
+{
+    if (nq && !offsets) raise(SW_ERR_VALUE, "%s: a NULL handle or array", what);
+    if (nq >= 0xFFFFFFFFull) raise(SW_ERR_VALUE, "%s: %llu queries exceed 32-bit indices", what, (unsigned long long)nq);
+    if (!nq) return;
+    if (offsets[0] != 0) raise(SW_ERR_VALUE, "%s: offsets must start at 0", what);
+    for (uint64_t q = 0; q < nq; ++q)
+        if (offsets[q] > offsets[q + 1]) raise(SW_ERR_VALUE, "%s: offsets must be non-decreasing (query %llu)", what, (unsigned long long)q);
+    if (offsets[nq] >= SCR_MAX_TEXT) raise(SW_ERR_VALUE, "%s: %llu bytes of query text; fewer than 2^32 - 256 are taken", what, (unsigned long long)offsets[nq]);
+    if (offsets[nq] && !blob) raise(SW_ERR_VALUE, "%s: a NULL handle or array", what);
+}
+
+void batch_best_hits(const sw_batch &b, const uint64_t *offsets, const char *blob, uint64_t nq, uint32_t k, sw_hits &o)
+{
+    const hipStream_t stream = HIT_STREAM;
+    const HostBatch &h = b.host;
+    const uint64_t n_asm = h.n_assemblies, n_cells = nq * n_asm;
+    if (n_cells >= 0xFFFFFFFFull) raise(SW_ERR_VALUE, "best hits: %llu queries x %llu assemblies exceed 32-bit cell indices", (unsigned long long)nq, (unsigned long long)n_asm);
+    o.nq = nq;
+    o.n_asm = n_asm;
+    o.k = k;
+    o.n_seeds.assign(nq, 0);
+    for (int f = 0; f < 5; ++f) {
+        o.field[f].alloc(n_cells);
+        if (n_cells) SW_HIP(hipMemsetAsync(o.field[f].p, (f == 0 || f == 2) ? 0 : 0xFF, n_cells * 4, stream));
+    }
+    // the key's fields: query | record | orientation | band, the band field one value wider than the largest band (b + 1 is looked at)
+    uint64_t max_q = 0, max_rec = 0;
+    for (uint64_t q = 0; q < nq; ++q) max_q = std::max(max_q, offsets[q + 1] - offsets[q]);
+    for (uint32_t l : h.rec_len) max_rec = std::max<uint64_t>(max_rec, l);
+    const uint32_t band_bits = bits_of(((max_rec + max_q) >> HIT_BAND_SHIFT) + 1), rec_bits = bits_of(h.rec_len.size() ? h.rec_len.size() - 1 : 0),
+                   q_bits = bits_of(nq ? nq - 1 : 0), key_bits = band_bits + 1 + rec_bits + q_bits;
+    if (key_bits > 64)
+        raise(SW_ERR_VALUE, "best hits: a hit key of %u bits (%u query, %u record, 1 orientation, %u band) does not fit 64", key_bits, q_bits, rec_bits, band_bits);
+    Event e0, e1;
+    SW_HIP(hipEventRecord(e0, stream));
+
+    // ---- query side: the screen's, then multiplicities and the seed table; the packed queries of Layer A ----
+    QuerySide Q;
+    build_query_side(offsets, blob, nq, k, stream, Q);
+    QueryPack P;
+    DevArray<uint32_t> seed_q, seed_i;
+    DevArray<uint8_t> seed_fc;
+    uint64_t n_seeds_total = 0;
+    if (Q.n_distinct) {
+        DevArray<uint32_t> mult(Q.n_distinct), d_ns(nq);
+        seed_q.alloc(Q.n_distinct);
+        seed_i.alloc(Q.n_distinct);
+        seed_fc.alloc(Q.n_distinct);
+        SW_HIP(hipMemsetAsync(mult.p, 0, Q.n_distinct * 4, stream));
+        SW_HIP(hipMemsetAsync(d_ns.p, 0, nq * 4, stream));
+        SW_HIP(hipMemsetAsync(seed_q.p, 0xFF, Q.n_distinct * 4, stream));
+        SW_HIP(hipMemsetAsync(seed_i.p, 0, Q.n_distinct * 4, stream));
+        SW_HIP(hipMemsetAsync(seed_fc.p, 0, Q.n_distinct, stream));
+        launch_1d(k_hit_mult, Q.n_valid, stream, (const uint32_t *)Q.sidx.p, (const uint32_t *)Q.number.p, mult.p);
+        launch_1d(k_hit_seeds, Q.n_valid, stream, (const uint32_t *)Q.sidx.p, (const uint32_t *)Q.number.p, (const uint32_t *)mult.p, (const uint64_t *)Q.by_number.p,
+                  (const uint32_t *)Q.vpos.p, (const uint8_t *)Q.text.p, (const uint64_t *)Q.d_off.p, (uint32_t)nq, k, seed_q.p, seed_i.p, seed_fc.p, d_ns.p);
+        SW_HIP(hipMemcpyAsync(o.n_seeds.data(), d_ns.p, nq * 4, hipMemcpyDeviceToHost, stream));
+        SW_HIP(hipStreamSynchronize(stream));
+        for (uint32_t s : o.n_seeds) n_seeds_total += s;
+    }
+    if (n_seeds_total) pack_queries(Q.text.p, offsets, nq, P);
+    SW_HIP(hipStreamSynchronize(stream));
+    Q.release_temporaries();
+    o.n_seeds_total = n_seeds_total;
+    SW_HIP(hipEventRecord(e1, stream));
+    SW_HIP(hipStreamSynchronize(stream));
+    float fms = 0;
+    SW_HIP(hipEventElapsedTime(&fms, e0, e1));
+    o.ms[0] = fms;
+
+    uint64_t hits = 0, chunks = 0, splits = 0, grows = 0, launches = 0, aligned = 0, striped = 0, cap_keys = 0;
+    if (n_seeds_total && n_asm) {
+        RunTiles T;
+        build_run_tiles(h, k, T);
+        DevRuns runs(b);
+        const uint64_t n_runs = T.n_runs;
+        // the buffer's budget changes speed only; SEQWIN_AMD_HIT_BUFFER_KB (test library) sets it.  Half of it holds keys, half the sort's second buffer
+        uint64_t budget = HIT_BUFFER_BYTES;
+        if (const char *e = SW_TEST_GETENV("SEQWIN_AMD_HIT_BUFFER_KB")) budget = scr_env_u64(e, budget >> 10) << 10;
+        cap_keys = std::min<uint64_t>(std::max<uint64_t>(budget / 16, 1), HIT_MAX_KEYS);
+        DevArray<uint64_t> buf_a(cap_keys), buf_b(cap_keys);
+        DevArray<uint64_t> d_run_base(n_runs);
+        DevArray<uint32_t> d_run_nk(n_runs), d_run_tile(n_runs + 1), d_run_rec(n_runs), d_run_pos(n_runs), d_fail(1), d_np(1);
+        DevArray<unsigned long long> d_cursor(1);
+        auto up = [&](void *dst, const void *src, size_t bytes) {
+            if (bytes) SW_HIP(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, stream));
+        };
+        up(d_run_base.p, T.run_base.data(), n_runs * 8);
+        up(d_run_nk.p, T.run_nk.data(), n_runs * 4);
+        up(d_run_tile.p, T.run_tile_off.data(), (n_runs + 1) * 4);
+        up(d_run_rec.p, T.run_rec.data(), n_runs * 4);
+        up(d_run_pos.p, T.run_pos.data(), n_runs * 4);
+        HitArgs g{};
+        g.packed = b.d_packed.p;
+        g.run_base = d_run_base.p;
+        g.run_nk = d_run_nk.p;
+        g.run_tile_off = d_run_tile.p;
+        g.run_rec = d_run_rec.p;
+        g.run_pos = d_run_pos.p;
+        g.n_runs = (uint32_t)n_runs;
+        g.t = Q.table();
+        g.seed_q = seed_q.p;
+        g.seed_i = seed_i.p;
+        g.seed_fc = seed_fc.p;
+        g.qoff = P.off.p;
+        g.cursor = d_cursor.p;
+        g.k = k;
+        g.band_bits = band_bits;
+        g.rec_bits = rec_bits;
+        const uint64_t tile_step = (uint64_t)hit_launch_blocks() * SCR_WPB;
+        Event c0, c1, c2, c3;
+        uint64_t rows = n_asm;
+        for (uint64_t a0 = 0; a0 < n_asm;) {
+            const uint64_t a1 = std::min<uint64_t>(n_asm, a0 + rows);
+            // probe: the chunk's tiles
+            SW_HIP(hipEventRecord(c0, stream));
+            SW_HIP(hipMemsetAsync(d_cursor.p, 0, 8, stream));
+            g.buf = buf_a.p;
+            g.cap = cap_keys;
+            for (uint64_t t0 = T.asm_tile_off[a0]; t0 < T.asm_tile_off[a1]; t0 += tile_step, ++launches) {
+                g.tile_begin = (uint32_t)t0;
+                g.tile_end = (uint32_t)std::min<uint64_t>(T.asm_tile_off[a1], t0 + tile_step);
+                const uint64_t n_tiles = (uint64_t)g.tile_end - g.tile_begin;
+                hipLaunchKernelGGL(k_hit_probe, dim3((unsigned)((n_tiles + SCR_WPB - 1) / SCR_WPB)), dim3(SCR_TPB), 0, stream, g);
+                SW_HIP(hipGetLastError());
+            }
+            unsigned long long n_hits = 0;
+            SW_HIP(hipMemcpyAsync(&n_hits, d_cursor.p, 8, hipMemcpyDeviceToHost, stream));
+            SW_HIP(hipEventRecord(c1, stream));
+            SW_HIP(hipStreamSynchronize(stream));
+            SW_HIP(hipEventElapsedTime(&fms, c0, c1));
+            o.ms[1] += fms;
+            if (n_hits > cap_keys) {
+                if (a1 - a0 > 1) {   // redone in two halves: the first now, the second is the next chunk
+                    rows = (a1 - a0 + 1) / 2;
+                    ++splits;
+                } else {             // one assembly above the budget: the buffer doubles
+                    if (cap_keys >= HIT_MAX_KEYS) raise(SW_ERR_VALUE, "best hits: assembly %llu alone has more than 2^31 hits", (unsigned long long)a0);
+                    cap_keys = std::min<uint64_t>(cap_keys * 2, HIT_MAX_KEYS);
+                    buf_a.alloc(cap_keys);
+                    buf_b.alloc(cap_keys);
+                    ++grows;
+                }
+                continue;
+            }
+            hits += n_hits;
+            o.chunk_hits.push_back(n_hits);
+            ++chunks;
+            if (n_hits) {
+                // sort over the used bits, run heads and lengths
+                uint64_t *kp = buf_a.p, *ap = buf_b.p;
+                if (n_hits > 1) {
+                    SW_HIP(hipMemsetAsync(d_fail.p, 0, 4, stream));
+                    sort_keys64(kp, ap, n_hits, 0, key_bits, stream, d_fail.p);
+                    uint32_t failed = 0;
+                    SW_HIP(hipMemcpyAsync(&failed, d_fail.p, 4, hipMemcpyDeviceToHost, stream));
+                    SW_HIP(hipStreamSynchronize(stream));
+                    check_sort_failed(failed);
+                }
+                DevArray<uint8_t> flag(n_hits);
+                DevArray<uint32_t> at(n_hits + 1);
+                launch_1d(k_scr_heads, n_hits, stream, (const uint64_t *)kp, 0u, flag.p);
+                const uint64_t n_runs_k = scan_flags(flag.p, at.p, n_hits, stream);
+                DevArray<uint64_t> ukey(n_runs_k);
+                DevArray<uint32_t> upos(n_runs_k);
+                launch_1d(k_scr_compact, n_hits, stream, (const uint8_t *)flag.p, (const uint32_t *)at.p, (const uint64_t *)kp, ukey.p, upos.p);
+                // vote
+                const uint64_t c_rows = a1 - a0, cells = nq * c_rows;
+                DevArray<unsigned long long> best(cells);
+                DevArray<sw_infix_pair> pairs(cells);
+                DevArray<uint32_t> out_idx(cells);
+                SW_HIP(hipMemsetAsync(best.p, 0, cells * 8, stream));
+                SW_HIP(hipMemsetAsync(d_np.p, 0, 4, stream));
+                {   // (one range: k_hit_vote reads `end` as the number of runs)
+                    const uint64_t blocks = (n_runs_k + SCR_TPB - 1) / SCR_TPB;
+                    hipLaunchKernelGGL(k_hit_vote, dim3((unsigned)blocks), dim3(SCR_TPB), 0, stream, (uint64_t)0, n_runs_k, (const uint64_t *)ukey.p,
+                                       (const uint32_t *)upos.p, (uint64_t)n_hits, (const uint32_t *)b.d_rec_asm.p, band_bits, rec_bits, (uint32_t)a0, (uint32_t)c_rows,
+                                       best.p);
+                    SW_HIP(hipGetLastError());
+                }
+                launch_1d(k_hit_finish, cells, stream, (const unsigned long long *)best.p, (const uint64_t *)ukey.p, (const uint64_t *)P.off.p,
+                          (const uint32_t *)runs.t.rec_len, k, band_bits, rec_bits, (uint32_t)a0, (uint32_t)c_rows, n_asm, o.field[0].p, o.field[1].p, o.field[2].p,
+                          pairs.p, out_idx.p, d_np.p);
+                uint32_t n_pairs = 0;
+                SW_HIP(hipMemcpyAsync(&n_pairs, d_np.p, 4, hipMemcpyDeviceToHost, stream));
+                SW_HIP(hipEventRecord(c2, stream));
+                SW_HIP(hipStreamSynchronize(stream));
+                SW_HIP(hipEventElapsedTime(&fms, c1, c2));
+                o.ms[2] += fms;
+                // Layer A on the chunk's winners
+                uint64_t cn[6] = {};
+                double dms[1] = {};
+                infix_device(runs.t, P, pairs.p, out_idx.p, n_pairs, o.field[4].p, o.field[3].p, cn, dms);
+                aligned += cn[0];
+                striped += cn[2];
+                o.ms[3] += dms[0];
+            }
+            a0 = a1;
+        }
+    }
+    SW_HIP(hipStreamSynchronize(stream));
+    const uint64_t cn[10] = {hits, n_seeds_total, chunks, splits, launches, aligned, striped, Q.n_distinct, cap_keys, grows};
+    memcpy(o.counters, cn, sizeof cn);
+}
+
+}  // namespace
+}  // namespace sw
+
+using namespace sw;
+
+extern "C" {
+
+int sw_batch_infix_distances(const sw_batch *b, const uint64_t *offsets, const char *blob, uint64_t n_queries, const sw_infix_pair *pairs, uint64_t n,
+                             uint32_t *dist, uint32_t *end, uint64_t *counters, double *ms)
+{
+    return guarded([&] {
+        check_queries("infix distances", offsets, blob, n_queries);
+        if (n && !pairs) raise(SW_ERR_VALUE, "infix distances: a NULL handle or array");
+        for (uint64_t i = 0; i < n; ++i)   // what a pair says by itself, before a handle or a device is touched
+            if (pairs[i].query >= n_queries || pairs[i].strand > 1 || pairs[i].start > pairs[i].stop)
+                raise(SW_ERR_VALUE, "infix distances: pair %llu (query %u, strand %u, record %u, [%u, %u)) names no query, no strand or no interval",
+                      (unsigned long long)i, pairs[i].query, pairs[i].strand, pairs[i].record, pairs[i].start, pairs[i].stop);
+        if (!b || (n && (!dist || !end))) raise(SW_ERR_VALUE, "infix distances: a NULL handle or array");
+        const std::vector<uint32_t> &rec_len = b->host.rec_len;
+        for (uint64_t i = 0; i < n; ++i)
+            if (pairs[i].record >= rec_len.size() || pairs[i].stop > rec_len[pairs[i].record])
+                raise(SW_ERR_VALUE, "infix distances: pair %llu (record %u, [%u, %u)) does not lie inside one of the batch's %llu records", (unsigned long long)i,
+                      pairs[i].record, pairs[i].start, pairs[i].stop, (unsigned long long)rec_len.size());
+        sq_require_device(b->device, "the batch");
+        StreamScope scope(HIT_STREAM);
+        DevRuns runs(*b);
+        const uint64_t total = n_queries ? offsets[n_queries] : 0;
+        DevArray<uint8_t> text(total);
+        if (total) SW_HIP(hipMemcpyAsync(text.p, blob, total, hipMemcpyHostToDevice, HIT_STREAM));
+        QueryPack P;
+        pack_queries(text.p, offsets, n_queries, P);
+        DevArray<sw_infix_pair> d_pairs(n);
+        DevArray<uint32_t> d_dist(n), d_end(n);
+        if (n) SW_HIP(hipMemcpyAsync(d_pairs.p, pairs, n * sizeof(sw_infix_pair), hipMemcpyHostToDevice, HIT_STREAM));
+        infix_device(runs.t, P, d_pairs.p, nullptr, n, d_dist.p, d_end.p, counters, ms);
+        if (n) {
+            SW_HIP(hipMemcpy(dist, d_dist.p, n * 4, hipMemcpyDeviceToHost));
+            SW_HIP(hipMemcpy(end, d_end.p, n * 4, hipMemcpyDeviceToHost));
+        }
+    });
+}
+
+int sw_batch_best_hits(const sw_batch *batch, const uint64_t *offsets, const char *blob, uint64_t n_queries, uint64_t k, sw_hits **out)
+{
+    return guarded([&] {
+        if (k < 1 || k > 32) raise(SW_ERR_VALUE, "best hits: k-mer length must lie in 1..32 (got %llu)", (unsigned long long)k);
+        if (!batch || !out) raise(SW_ERR_VALUE, "best hits: a NULL handle or array");
+        check_queries("best hits", offsets, blob, n_queries);
+        if (batch->host.rec_len.size() && !batch->d_packed.p) raise(SW_ERR_VALUE, "best hits: the batch holds no packed bases (it must be resident)");
+        scr_require_device(batch->device, "the batch");
+        StreamScope scope(HIT_STREAM);
+        std::unique_ptr<sw_hits> o(new sw_hits);
+        o->device = batch->device;
+        batch_best_hits(*batch, offsets, blob, n_queries, (uint32_t)k, *o);
+        *out = o.release();
+    });
+}
+
+int sw_hits_sizes(const sw_hits *h, uint64_t *n_queries, uint64_t *n_assemblies, uint64_t *n_seeds, uint64_t *k)
+{
+    return guarded([&] {
+        if (!h) raise(SW_ERR_VALUE, "best hits: a NULL handle");
+        if (n_queries) *n_queries = h->nq;
+        if (n_assemblies) *n_assemblies = h->n_asm;
+        if (n_seeds) *n_seeds = h->n_seeds_total;
+        if (k) *k = h->k;
+    });
+}
+
+int sw_hits_n_seeds(const sw_hits *h, uint32_t *n_seeds)
+{
+    return guarded([&] {
+        if (!h || (h->nq && !n_seeds)) raise(SW_ERR_VALUE, "best hits: a NULL handle or array");
+        if (h->nq) memcpy(n_seeds, h->n_seeds.data(), h->nq * 4);
+    });
+}
+
+int sw_hits_block(const sw_hits *h, uint64_t field, uint64_t r0, uint64_t r1, uint64_t c0, uint64_t c1, uint32_t *out)
+{
+    return guarded([&] {
+        if (!h) raise(SW_ERR_VALUE, "best hits: a NULL handle");
+        if (field > 4) raise(SW_ERR_VALUE, "best hits: field %llu is none of seeds, record, strand, end, dist (0..4)", (unsigned long long)field);
+        if (r0 > r1 || r1 > h->nq || c0 > c1 || c1 > h->n_asm)
+            raise(SW_ERR_VALUE, "best hits: rows [%llu, %llu) x columns [%llu, %llu) lie outside the %llu queries x %llu assemblies", (unsigned long long)r0,
+                  (unsigned long long)r1, (unsigned long long)c0, (unsigned long long)c1, (unsigned long long)h->nq, (unsigned long long)h->n_asm);
+        const uint64_t nr = r1 - r0, nc = c1 - c0;
+        if (!nr || !nc) return;
+        if (!out) raise(SW_ERR_VALUE, "best hits: a NULL handle or array");
+        scr_require_device(h->device, "the hits");
+        SW_HIP(hipMemcpy2D(out, nc * 4, h->field[field].p + r0 * h->n_asm + c0, h->n_asm * 4, nc * 4, nr, hipMemcpyDeviceToHost));
+    });
+}
+
+int sw_hits_stats(const sw_hits *h, uint64_t *counters, double *ms)
+{
+    return guarded([&] {
+        if (!h) raise(SW_ERR_VALUE, "best hits: a NULL handle");
+        if (counters) memcpy(counters, h->counters, sizeof h->counters);
+        if (ms) memcpy(ms, h->ms, sizeof h->ms);
+    });
+}
+
+int sw_hits_chunk_hits(const sw_hits *h, uint64_t *hits)
+{
+    return guarded([&] {
+        if (!h) raise(SW_ERR_VALUE, "best hits: a NULL handle");
+        if (hits && !h->chunk_hits.empty()) memcpy(hits, h->chunk_hits.data(), h->chunk_hits.size() * 8);
+    });
+}
+
+void sw_hits_free(sw_hits *h)
+{
+    delete h;
+}
+
+}  // extern "C"

@@ -132,6 +132,37 @@ class Batch:
         check(lib.sw_batch_screen(self._h, _ptr(offs), b"".join(qs), c_u64(len(qs)), c_u64(int(kmerlen)), c_vp(stream), ctypes.byref(h)))
         return Screen(h)
 
+    def infix_distances(self, queries, pairs, stats: bool = False):
+        """``(dist, end)`` of the infix edit distance of queries against intervals of the batch (csrc/hits.hip, DESIGN.md section
+        3.2e).  ``pairs`` is INFIX_PAIR_DTYPE or an (n, 5) array of ``(query, strand, record, start, stop)``: the pattern is the
+        query (strand 0) or its reverse complement (strand 1), the text bases ``[start, stop)`` of the global record.  ``dist`` is
+        the smallest unit-cost edit distance of the whole pattern to any substring of the text, ``end`` the record position behind
+        the first text prefix that attains it.  An empty query gives ``(0, start)``, an empty text ``(len(query), start)``.  Not
+        BLAST.  ValueError for a pair that names no query, no strand or no interval of its record."""
+        offs, blob, nq = _query_csr(queries)
+        pr = _infix_pairs(pairs)
+        dist = np.empty(len(pr), np.uint32)
+        end = np.empty(len(pr), np.uint32)
+        c = (c_u64 * 6)()
+        ms = (ctypes.c_double * 1)()
+        check(lib.sw_batch_infix_distances(self._h, _ptr(offs), blob, c_u64(nq), _ptr(pr), c_u64(len(pr)), _ptr(dist), _ptr(end), c, ms))
+        if not stats:
+            return dist, end
+        d = dict(zip(("pairs", "cells", "striped_pairs", "longest", "launches", "block_cap"), (int(x) for x in c)))
+        d.update(distance_ms=ms[0])
+        return dist, end, d
+
+    def best_hits(self, queries, kmerlen: int) -> "BestHits":
+        """For every query (a list of ``str`` or ``bytes``) and every assembly: the best seeded locus and the exact infix edit
+        distance of the query to the best substring there (csrc/hits.hip).  A seed is a canonical
+        ``kmerlen``-mer that exactly one window of ALL the query text has and that is not its own reverse complement: a query whose
+        k-mers are shared with another query, or repeat inside it, loses them as seeds -- deliberately, one hit means one diagonal.
+        Not BLAST: no scores, no e-values, no local alignment, one locus per pair.  ValueError for a k-mer length outside 1..32."""
+        offs, blob, nq = _query_csr(queries)
+        h = c_vp()
+        check(lib.sw_batch_best_hits(self._h, _ptr(offs), blob, c_u64(nq), c_u64(int(kmerlen)), ctypes.byref(h)))
+        return BestHits(h)
+
     def fetch(self, intervals, stats: bool = False):
         """The text of ``intervals`` (INTERVAL_DTYPE or an (n, 3) array of record, start, stop; ``record`` is the batch's global
         record index), decoded from the resident packed bases (csrc/seqs.hip): ``(offsets, blob, inexact)`` -- interval i is
@@ -170,6 +201,29 @@ class Batch:
 
 INTERVAL_DTYPE = np.dtype([("record", "<u4"), ("start", "<u4"), ("stop", "<u4")])
 SEQ_INEXACT = 1
+INFIX_PAIR_DTYPE = np.dtype([("query", "<u4"), ("strand", "<u4"), ("record", "<u4"), ("start", "<u4"), ("stop", "<u4")])
+NO_HIT = 0xFFFFFFFF   # record, end and dist of a (query, assembly) without a hit
+
+
+def _query_csr(queries):
+    """(offsets uint64[n + 1], blob, n) of a list of ``str`` or ``bytes``."""
+    qs = [q.encode("utf-8") if isinstance(q, str) else bytes(q) for q in queries]
+    offs = np.zeros(len(qs) + 1, np.uint64)
+    np.cumsum([len(q) for q in qs], out=offs[1:])
+    return offs, b"".join(qs), len(qs)
+
+
+def _infix_pairs(pairs) -> np.ndarray:
+    a = np.asarray(pairs)
+    if a.dtype != INFIX_PAIR_DTYPE:
+        a = np.asarray(a, np.int64).reshape(-1, 5)
+        if a.size and (a.min() < 0 or a.max() > 0xFFFFFFFF):
+            raise ValueError("query, strand, record, start and stop of a pair are 32-bit values")
+        out = np.empty(len(a), INFIX_PAIR_DTYPE)
+        for i, f in enumerate(INFIX_PAIR_DTYPE.names):
+            out[f] = a[:, i]
+        a = out
+    return np.ascontiguousarray(a)
 
 
 def _intervals(iv) -> np.ndarray:
@@ -547,6 +601,13 @@ class Markers:
         o = offs.astype(np.int64)
         return batch.screen([blob[o[i]:o[i + 1]] for i in range(len(o) - 1)], kmerlen)
 
+    def best_hits(self, batch: "Batch", kmerlen: int, select=None) -> "BestHits":
+        """:meth:`Batch.best_hits` of the representatives' text -- ``sequences(batch, "reps", select)``, in that order -- against
+        every assembly of ``batch``.  ``kmerlen`` is the caller's choice; it need not be the graph's k."""
+        offs, blob, _ = self.sequences(batch, "reps", select)
+        o = offs.astype(np.int64)
+        return batch.best_hits([blob[o[i]:o[i + 1]] for i in range(len(o) - 1)], kmerlen)
+
     def candidates(self, min_len: int) -> np.ndarray:
         """Indices of the subgraphs the reference keeps (markers.py:514-517): len >= min_len, neither single nor dup."""
         reps = self.reps()[0]
@@ -745,6 +806,76 @@ class Screen:
     def close(self) -> None:
         if self._h:
             lib.sw_screen_free(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class BestHits:
+    """The best hit of every query in every assembly of a batch, resident on the device (:meth:`Batch.best_hits`,
+    :meth:`Markers.best_hits`; csrc/hits.hip): per (query, assembly) the winning locus' vote ``seeds``, its
+    global ``record`` and ``strand``, and the infix edit distance ``dist`` of the query to the best substring of the locus' window,
+    which ends at record position ``end``.  A pair without a hit reads seeds 0, strand 0 and NO_HIT elsewhere.  It covers the ground
+    of ``eval_markers`` (src/seqwin/markers.py:607-696), has no counterpart in the reference, is not BLAST and fills none of
+    ``MarkerMetrics``.  A single-device object on a resident batch.  ``rows`` (queries) / ``cols`` (assemblies) are None (all), a
+    ``(lo, hi)`` pair, a slice or a range."""
+
+    def __init__(self, handle: c_vp):
+        self._h = handle
+
+    def sizes(self):
+        """(queries, assemblies, seeds of all queries, k)"""
+        v = [c_u64() for _ in range(4)]
+        check(lib.sw_hits_sizes(self._h, *[ctypes.byref(x) for x in v]))
+        return tuple(x.value for x in v)
+
+    def n_seeds(self) -> np.ndarray:
+        """uint32[queries]: the canonical k-mers of every query that no other window of the query text has."""
+        out = np.empty(self.sizes()[0], np.uint32)
+        check(lib.sw_hits_n_seeds(self._h, _ptr(out)))
+        return out
+
+    def _block(self, field: int, rows, cols) -> np.ndarray:
+        nq, na, _, _ = self.sizes()
+        (r0, r1), (c0, c1) = _block_range(rows, nq), _block_range(cols, na)
+        out = np.empty((max(r1 - r0, 0), max(c1 - c0, 0)), np.uint32)
+        check(lib.sw_hits_block(self._h, c_u64(field), c_u64(r0), c_u64(r1), c_u64(c0), c_u64(c1), _ptr(out)))
+        return out
+
+    def seeds(self, rows=None, cols=None) -> np.ndarray:
+        """uint32[rows, cols]: the winner's vote (hits of its band and the next); 0: no hit."""
+        return self._block(0, rows, cols)
+
+    def record(self, rows=None, cols=None) -> np.ndarray:
+        return self._block(1, rows, cols)
+
+    def strand(self, rows=None, cols=None) -> np.ndarray:
+        return self._block(2, rows, cols).astype(np.uint8)
+
+    def end(self, rows=None, cols=None) -> np.ndarray:
+        return self._block(3, rows, cols)
+
+    def dist(self, rows=None, cols=None) -> np.ndarray:
+        return self._block(4, rows, cols)
+
+    def stats(self) -> dict:
+        c = (c_u64 * 10)()
+        ms = (ctypes.c_double * 4)()
+        check(lib.sw_hits_stats(self._h, c, ms))
+        d = dict(zip(("hits", "seeds", "chunks", "chunk_splits", "launches", "pairs_aligned", "striped_pairs", "distinct_kmers", "buffer_keys",
+                      "buffer_doublings"), (int(x) for x in c)))
+        per = (c_u64 * max(d["chunks"], 1))()
+        check(lib.sw_hits_chunk_hits(self._h, per))
+        d.update(query_ms=ms[0], probe_ms=ms[1], vote_ms=ms[2], distance_ms=ms[3], chunk_hits=[int(x) for x in per][:d["chunks"]])
+        return d
+
+    def close(self) -> None:
+        if self._h:
+            lib.sw_hits_free(self._h)
             self._h = None
 
     def __del__(self):

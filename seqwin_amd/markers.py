@@ -207,3 +207,38 @@ def screen_summary(screen, n_tar: int, min_containment: float = 0.9) -> np.ndarr
         out[name] = block.sum(axis=1) / block.shape[1]
         out[f_name] = np.where(np.isnan(nk), np.nan, (block >= np.float64(min_containment)).sum(axis=1) / block.shape[1])
     return out
+
+
+HIT_SUMMARY_DTYPE = np.dtype([("similarity_tar", "<f8"), ("f_tar", "<f8"), ("distance_neg", "<f8"), ("f_neg", "<f8")])
+
+
+def hit_summary(h, lengths, n_tar: int, min_identity: float = 0.9) -> np.ndarray:
+    """Per query of a :class:`BestHits` (or of a uint32 ``dist`` matrix of host memory, 0xFFFFFFFF = no hit), with ``lengths`` the
+    queries' lengths, the targets the first ``n_tar`` columns and the non-targets the rest: ``similarity_tar`` = the mean over the
+    targets of ``max(0, 1 - dist / len)`` with 0 where there is no hit, ``distance_neg`` = the mean over the non-targets of
+    ``min(1, dist / len)`` with 1 where there is no hit, ``f_tar`` / ``f_neg`` = the share of the group's assemblies with a hit and
+    ``dist <= (1 - min_identity) * len``, all in float64.  A query of length 0, and an empty group, read ``nan``.  The names are
+    deliberately not those of ``MarkerMetrics``: an infix edit distance at one seeded locus is not BLAST's best hit, and nothing
+    of this is written into ``signatures.csv``."""
+    dist = np.asarray(h.dist() if hasattr(h, "dist") else h, np.uint32)
+    lengths = np.asarray(lengths, np.int64).reshape(-1)
+    if dist.ndim != 2 or lengths.shape != (dist.shape[0],) or (lengths < 0).any():
+        raise ValueError(f"dist of shape {dist.shape} against {lengths.shape} query lengths")
+    n_tar = int(n_tar)
+    if not 0 <= n_tar <= dist.shape[1]:
+        raise ValueError(f"n_tar = {n_tar} lies outside the {dist.shape[1]} assemblies")
+    out = np.zeros(len(lengths), HIT_SUMMARY_DTYPE)
+    ln = lengths.astype(np.float64)
+    ln[ln == 0] = np.nan
+    hit = dist != np.uint32(0xFFFFFFFF)
+    frac = np.where(hit, dist.astype(np.float64), np.inf) / ln[:, None]          # dist / len; inf without a hit, nan for an empty query
+    near = hit & (dist.astype(np.float64) <= (1.0 - np.float64(min_identity)) * ln[:, None])
+    for name, f_name, cols, val in (("similarity_tar", "f_tar", slice(0, n_tar), np.maximum(0.0, 1.0 - frac)),
+                                    ("distance_neg", "f_neg", slice(n_tar, None), np.minimum(1.0, frac))):
+        block = val[:, cols]
+        if block.shape[1] == 0:
+            out[name] = out[f_name] = np.nan
+            continue
+        out[name] = block.sum(axis=1) / block.shape[1]
+        out[f_name] = np.where(np.isnan(ln), np.nan, near[:, cols].sum(axis=1) / block.shape[1])
+    return out
