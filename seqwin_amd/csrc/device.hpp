@@ -19,6 +19,34 @@ namespace sw {
                         __FILE__, __LINE__, #expr);                                                    \
     } while (0)
 
+// ---- small host helpers of every C-ABI file -----------------------------------------------------------------------------------
+// the decimal number in v; dflt if v is unset, empty or no number
+inline uint64_t env_u64(const char *v, uint64_t dflt)
+{
+    if (!v || !*v) return dflt;
+    char *end = nullptr;
+    const unsigned long long x = strtoull(v, &end, 10);
+    return (end && *end == 0) ? (uint64_t)x : dflt;
+}
+
+// a handle's arrays are read on the calling thread's current device: it must be the handle's
+inline void require_device(int device, const char *what)
+{
+    int cur = -1;
+    SW_HIP(hipGetDevice(&cur));
+    if (cur != device)
+        raise(SW_ERR_VALUE, "%s lives on device %d but the calling thread's current device is %d (sw_set_device)", what, device, cur);
+}
+
+constexpr uint32_t MAX_LAUNCH_BLOCKS = 1u << 22;   // workgroups per launch: 2^30 threads of 256, below the 2^32 a launch may hold
+
+// workgroups per launch; the switch named env_name (test library) lowers it, so that a small input needs several launches -- what
+// the 15 000-genome set needs by its size
+inline uint32_t launch_blocks(const char *env_name)
+{
+    return (uint32_t)std::max<uint64_t>(std::min<uint64_t>(env_u64(SW_TEST_GETENV(env_name), MAX_LAUNCH_BLOCKS), MAX_LAUNCH_BLOCKS), 1);
+}
+
 // ---- position-dependent checksums of the output arrays (r06: EVERY field of an element enters together with the element's index) ----
 // Element i of array X contributes  sum over its fields f of  mix64(((base + i) * G ^ K_f) + value_f)  (mod 2^64), so two
 // elements that swap ANY field -- a node's start / stop / counts / penalty, an edge's second / weight -- change the sum (until r05

@@ -14,8 +14,8 @@
 // Layer B, seed vote (sw_batch_best_hits): the query side is the screen's (screen_core.hpp); a canonical word that exactly one
 // valid window of all query text has, and that is not its own reverse complement, is a seed.
 //   k_hit_mult / k_hit_seeds   windows per distinct word; (query, offset, window-is-canonical) per seed
-//   k_hit_probe    k_scr_probe's run / tile / lane walk with its 16 grouped first-slot loads; a hit appends the 64-bit key
-//                  (query | record | orientation | band) to the hit buffer: one atomic on the cursor per wave
+//   k_hit_probe    the batch's run / tile / lane walk (kmer_walk.hpp) with k_scr_probe's 16 grouped first-slot loads; a hit appends
+//                  the 64-bit key (query | record | orientation | band) to the hit buffer: one atomic on the cursor per wave
 //   per chunk of assemblies: the keys sorted over their used bits, run heads and lengths, k_hit_vote (score = run + next band's run,
 //   the winner of a (query, assembly) by atomicMax of (score, ~run index): the smallest key wins a tie), k_hit_finish (the winner's
 //   fields, its window as a pair of Layer A), and Layer A on the chunk's pairs.  A chunk whose hits overflow the buffer is redone in
@@ -32,12 +32,6 @@ constexpr uint64_t HIT_BUFFER_BYTES = 1ull << 30;      // hit keys and the sort'
 constexpr uint64_t HIT_MAX_KEYS = 1ull << 31;          // a run index and a score are 32-bit values
 constexpr uint32_t IX_CLASSES = 8;                     // group widths 1, 2, ... 64, then the striped route
 constexpr uint32_t IX_STRIPE_GROUPS = 1024;
-
-// workgroups per launch of the probe kernel; SEQWIN_AMD_HIT_MAX_BLOCKS (test library) lowers it
-uint32_t hit_launch_blocks()
-{
-    return (uint32_t)std::max<uint64_t>(std::min<uint64_t>(scr_env_u64(SW_TEST_GETENV("SEQWIN_AMD_HIT_MAX_BLOCKS"), SCR_MAX_BLOCKS), SCR_MAX_BLOCKS), 1);
-}
 
 uint32_t bits_of(uint64_t x)   // bits that hold 0 .. x
 {
@@ -292,7 +286,7 @@ void infix_device(const RunTable &t, const QueryPack &P, const sw_infix_pair *d_
         a.out_idx = d_out_idx;
         a.dist = d_dist;
         a.end = d_end;
-        const uint64_t max_threads = (uint64_t)sq_launch_blocks() * SQ_TPB;
+        const uint64_t max_threads = (uint64_t)launch_blocks(SQ_BLOCKS_ENV) * SQ_TPB;
         for (uint32_t c = 0; c + 1 < IX_CLASSES; ++c) {   // register route, g = 2^c lanes per pair
             const uint64_t cnt = stat[c], g = 1ull << c, per_launch = std::max<uint64_t>(max_threads / g, 1);
             for (uint64_t x0 = 0; x0 < cnt; x0 += per_launch, ++launches) {
@@ -372,10 +366,7 @@ __global__ __launch_bounds__(SCR_TPB) void k_hit_seeds(uint64_t base, uint64_t e
 
 // ---- Layer B: probe -------------------------------------------------------------------------------------------------------------
 struct HitArgs {
-    const uint32_t *packed;
-    const uint64_t *run_base;
-    const uint32_t *run_nk, *run_tile_off, *run_rec, *run_pos;
-    uint32_t n_runs, tile_begin, tile_end;
+    RunView v;                       // with run_rec / run_pos
     Table t;
     const uint32_t *seed_q, *seed_i;
     const uint8_t *seed_fc;
@@ -388,49 +379,27 @@ struct HitArgs {
 
 __global__ __launch_bounds__(SCR_TPB) void k_hit_probe(HitArgs g)
 {
-    const uint32_t wave = threadIdx.x / SCR_WAVE, lane = threadIdx.x % SCR_WAVE;
-    const uint64_t tile64 = (uint64_t)g.tile_begin + (uint64_t)blockIdx.x * SCR_WPB + wave;
-    if (tile64 >= g.tile_end) return;   // (the whole wave)
     if (*(volatile unsigned long long *)g.cursor > g.cap) return;   // (the whole wave: the chunk has overflowed, it is redone anyway)
-    const uint32_t tile = (uint32_t)tile64;
-    uint32_t lo = 0, hi = g.n_runs;     // the last run whose first tile is <= tile
-    while (lo + 1 < hi) {
-        const uint32_t mid = (lo + hi) >> 1;
-        if (g.run_tile_off[mid] <= tile) lo = mid; else hi = mid;
-    }
-    const uint32_t r = lo, nk = g.run_nk[r];
-    const uint64_t first = (uint64_t)(tile - g.run_tile_off[r]) * SCR_TILE + (uint64_t)lane * SCR_L;
-    const uint32_t n_mine = first < nk ? (uint32_t)(nk - first < SCR_L ? nk - first : SCR_L) : 0;
+    const uint32_t lane = threadIdx.x % SCR_WAVE;
+    uint32_t r, n_mine;
+    uint64_t first;
+    if (!wave_tile(g.v, lane, r, first, n_mine)) return;   // (the whole wave)
     const uint32_t k = g.k;
-    const uint64_t mask = k >= 32 ? ~0ull : (1ull << (2 * k)) - 1;
-    const uint32_t sh = 2 * (k - 1);
     uint64_t key[SCR_L];
     uint32_t have = 0, cnt = 0;         // bit j: key[j] is a hit
+    KmerRoller R(g.v.packed, k);
     if (n_mine) {
-        uint64_t pos = g.run_base[r] + first, fwd = 0, rev = 0;
-        uint32_t w = g.packed[pos >> 4] >> (2 * (uint32_t)(pos & 15)), left = 16 - (uint32_t)(pos & 15);
-        auto roll = [&]() {
-            if (left == 0) {
-                w = g.packed[pos >> 4];
-                left = 16;
-            }
-            const uint64_t c = w & 3u;
-            w >>= 2;
-            --left;
-            ++pos;
-            fwd = ((fwd << 2) | c) & mask;
-            rev = (rev >> 2) | ((3 - c) << sh);
-        };
-        for (uint32_t i = 0; i + 1 < k; ++i) roll();
+        R.start(g.v.run_base[r] + first);
+        for (uint32_t i = 0; i + 1 < k; ++i) R.roll();
         uint64_t canon[SCR_L];
         uint32_t home[SCR_L], slot[SCR_L], is_fwd = 0;
 #pragma unroll
         for (uint32_t j = 0; j < SCR_L; ++j) {
             canon[j] = 0;
             if (j < n_mine) {
-                roll();
-                canon[j] = fwd < rev ? fwd : rev;
-                is_fwd |= (fwd < rev ? 1u : 0u) << j;
+                R.roll();
+                canon[j] = R.fwd < R.rev ? R.fwd : R.rev;
+                is_fwd |= (R.fwd < R.rev ? 1u : 0u) << j;
             }
         }
 #pragma unroll
@@ -438,8 +407,8 @@ __global__ __launch_bounds__(SCR_TPB) void k_hit_probe(HitArgs g)
             home[j] = scr_home(canon[j], g.t.bits);
             slot[j] = j < n_mine ? g.t.slots[home[j]] : 0u;
         }
-        const uint32_t rec = g.run_rec[r];
-        const uint64_t p0 = (uint64_t)g.run_pos[r] + first;
+        const uint32_t rec = g.v.run_rec[r];
+        const uint64_t p0 = (uint64_t)g.v.run_pos[r] + first;
 #pragma unroll
         for (uint32_t j = 0; j < SCR_L; ++j) {
             key[j] = 0;
@@ -456,19 +425,10 @@ __global__ __launch_bounds__(SCR_TPB) void k_hit_probe(HitArgs g)
             ++cnt;
         }
     }
-    // one atomic on the cursor per wave: the lanes' counts scanned, the wave's range claimed by lane 0
-    uint32_t incl = cnt;
-    for (uint32_t d = 1; d < SCR_WAVE; d <<= 1) {
-        const uint32_t o = __shfl_up(incl, d, SCR_WAVE);
-        if (lane >= d) incl += o;
-    }
-    const uint32_t total = __shfl(incl, SCR_WAVE - 1, SCR_WAVE);
-    if (!total) return;   // (uniform)
-    unsigned long long at = 0;
-    if (lane == 0) at = atomicAdd(g.cursor, (unsigned long long)total);
-    at = __shfl(at, 0, SCR_WAVE);
-    if (at + total > g.cap) return;   // (uniform) overflow: the host reads it from the cursor
-    at += incl - cnt;
+    const WaveRange w = wave_append(g.cursor, lane, cnt);   // one atomic on the cursor per wave
+    if (!w.total) return;                             // (uniform)
+    if (w.base + w.total > g.cap) return;             // (uniform) overflow: the host reads it from the cursor
+    unsigned long long at = w.base + w.offset;
 #pragma unroll
     for (uint32_t j = 0; j < SCR_L; ++j)
         if ((have >> j) & 1u) g.buf[at++] = key[j];
@@ -533,18 +493,6 @@ struct sw_hits {
 namespace sw {
 namespace {
 
-void check_queries(const char *what, const uint64_t *offsets, const char *blob, uint64_t nq)
-{
-    if (nq && !offsets) raise(SW_ERR_VALUE, "%s: a NULL handle or array", what);
-    if (nq >= 0xFFFFFFFFull) raise(SW_ERR_VALUE, "%s: %llu queries exceed 32-bit indices", what, (unsigned long long)nq);
-    if (!nq) return;
-    if (offsets[0] != 0) raise(SW_ERR_VALUE, "%s: offsets must start at 0", what);
-    for (uint64_t q = 0; q < nq; ++q)
-        if (offsets[q] > offsets[q + 1]) raise(SW_ERR_VALUE, "%s: offsets must be non-decreasing (query %llu)", what, (unsigned long long)q);
-    if (offsets[nq] >= SCR_MAX_TEXT) raise(SW_ERR_VALUE, "%s: %llu bytes of query text; fewer than 2^32 - 256 are taken", what, (unsigned long long)offsets[nq]);
-    if (offsets[nq] && !blob) raise(SW_ERR_VALUE, "%s: a NULL handle or array", what);
-}
-
 void batch_best_hits(const sw_batch &b, const uint64_t *offsets, const char *blob, uint64_t nq, uint32_t k, sw_hits &o)
 {
     const hipStream_t stream = HIT_STREAM;
@@ -607,33 +555,17 @@ void batch_best_hits(const sw_batch &b, const uint64_t *offsets, const char *blo
     uint64_t hits = 0, chunks = 0, splits = 0, grows = 0, launches = 0, aligned = 0, striped = 0, cap_keys = 0;
     if (n_seeds_total && n_asm) {
         RunTiles T;
-        build_run_tiles(h, k, T);
+        build_run_tiles(h, k, "best hits", T);
         DevRuns runs(b);
-        const uint64_t n_runs = T.n_runs;
         // the buffer's budget changes speed only; SEQWIN_AMD_HIT_BUFFER_KB (test library) sets it.  Half of it holds keys, half the sort's second buffer
         uint64_t budget = HIT_BUFFER_BYTES;
-        if (const char *e = SW_TEST_GETENV("SEQWIN_AMD_HIT_BUFFER_KB")) budget = scr_env_u64(e, budget >> 10) << 10;
+        if (const char *e = SW_TEST_GETENV("SEQWIN_AMD_HIT_BUFFER_KB")) budget = env_u64(e, budget >> 10) << 10;
         cap_keys = std::min<uint64_t>(std::max<uint64_t>(budget / 16, 1), HIT_MAX_KEYS);
         DevArray<uint64_t> buf_a(cap_keys), buf_b(cap_keys);
-        DevArray<uint64_t> d_run_base(n_runs);
-        DevArray<uint32_t> d_run_nk(n_runs), d_run_tile(n_runs + 1), d_run_rec(n_runs), d_run_pos(n_runs), d_fail(1), d_np(1);
+        DevArray<uint32_t> d_fail(1), d_np(1);
         DevArray<unsigned long long> d_cursor(1);
-        auto up = [&](void *dst, const void *src, size_t bytes) {
-            if (bytes) SW_HIP(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, stream));
-        };
-        up(d_run_base.p, T.run_base.data(), n_runs * 8);
-        up(d_run_nk.p, T.run_nk.data(), n_runs * 4);
-        up(d_run_tile.p, T.run_tile_off.data(), (n_runs + 1) * 4);
-        up(d_run_rec.p, T.run_rec.data(), n_runs * 4);
-        up(d_run_pos.p, T.run_pos.data(), n_runs * 4);
+        DevRunTiles tiles(T, b.d_packed.p, stream, true);
         HitArgs g{};
-        g.packed = b.d_packed.p;
-        g.run_base = d_run_base.p;
-        g.run_nk = d_run_nk.p;
-        g.run_tile_off = d_run_tile.p;
-        g.run_rec = d_run_rec.p;
-        g.run_pos = d_run_pos.p;
-        g.n_runs = (uint32_t)n_runs;
         g.t = Q.table();
         g.seed_q = seed_q.p;
         g.seed_i = seed_i.p;
@@ -643,7 +575,7 @@ void batch_best_hits(const sw_batch &b, const uint64_t *offsets, const char *blo
         g.k = k;
         g.band_bits = band_bits;
         g.rec_bits = rec_bits;
-        const uint64_t tile_step = (uint64_t)hit_launch_blocks() * SCR_WPB;
+        const uint32_t blocks_max = launch_blocks("SEQWIN_AMD_HIT_MAX_BLOCKS");   // the probe kernel's; the switch (test library) lowers it
         Event c0, c1, c2, c3;
         uint64_t rows = n_asm;
         for (uint64_t a0 = 0; a0 < n_asm;) {
@@ -653,13 +585,8 @@ void batch_best_hits(const sw_batch &b, const uint64_t *offsets, const char *blo
             SW_HIP(hipMemsetAsync(d_cursor.p, 0, 8, stream));
             g.buf = buf_a.p;
             g.cap = cap_keys;
-            for (uint64_t t0 = T.asm_tile_off[a0]; t0 < T.asm_tile_off[a1]; t0 += tile_step, ++launches) {
-                g.tile_begin = (uint32_t)t0;
-                g.tile_end = (uint32_t)std::min<uint64_t>(T.asm_tile_off[a1], t0 + tile_step);
-                const uint64_t n_tiles = (uint64_t)g.tile_end - g.tile_begin;
-                hipLaunchKernelGGL(k_hit_probe, dim3((unsigned)((n_tiles + SCR_WPB - 1) / SCR_WPB)), dim3(SCR_TPB), 0, stream, g);
-                SW_HIP(hipGetLastError());
-            }
+            g.v = tiles.view(T.asm_tile_off[a0], T.asm_tile_off[a1]);
+            launches += launch_tiles(k_hit_probe, g, blocks_max, stream);
             unsigned long long n_hits = 0;
             SW_HIP(hipMemcpyAsync(&n_hits, d_cursor.p, 8, hipMemcpyDeviceToHost, stream));
             SW_HIP(hipEventRecord(c1, stream));
@@ -762,7 +689,7 @@ int sw_batch_infix_distances(const sw_batch *b, const uint64_t *offsets, const c
             if (pairs[i].record >= rec_len.size() || pairs[i].stop > rec_len[pairs[i].record])
                 raise(SW_ERR_VALUE, "infix distances: pair %llu (record %u, [%u, %u)) does not lie inside one of the batch's %llu records", (unsigned long long)i,
                       pairs[i].record, pairs[i].start, pairs[i].stop, (unsigned long long)rec_len.size());
-        sq_require_device(b->device, "the batch");
+        require_device(b->device, "the batch");
         StreamScope scope(HIT_STREAM);
         DevRuns runs(*b);
         const uint64_t total = n_queries ? offsets[n_queries] : 0;
@@ -788,7 +715,7 @@ int sw_batch_best_hits(const sw_batch *batch, const uint64_t *offsets, const cha
         if (!batch || !out) raise(SW_ERR_VALUE, "best hits: a NULL handle or array");
         check_queries("best hits", offsets, blob, n_queries);
         if (batch->host.rec_len.size() && !batch->d_packed.p) raise(SW_ERR_VALUE, "best hits: the batch holds no packed bases (it must be resident)");
-        scr_require_device(batch->device, "the batch");
+        require_device(batch->device, "the batch");
         StreamScope scope(HIT_STREAM);
         std::unique_ptr<sw_hits> o(new sw_hits);
         o->device = batch->device;
@@ -827,7 +754,7 @@ int sw_hits_block(const sw_hits *h, uint64_t field, uint64_t r0, uint64_t r1, ui
         const uint64_t nr = r1 - r0, nc = c1 - c0;
         if (!nr || !nc) return;
         if (!out) raise(SW_ERR_VALUE, "best hits: a NULL handle or array");
-        scr_require_device(h->device, "the hits");
+        require_device(h->device, "the hits");
         SW_HIP(hipMemcpy2D(out, nc * 4, h->field[field].p + r0 * h->n_asm + c0, h->n_asm * 4, nc * 4, nr, hipMemcpyDeviceToHost));
     });
 }

@@ -37,22 +37,6 @@ constexpr uint32_t FLAG_SINGLE = 1, FLAG_DUP = 2, FLAG_NO_TARGET = 4;
 
 inline unsigned mk_blocks(uint64_t n) { return (unsigned)((n + MK_TPB - 1) / MK_TPB); }
 
-uint64_t mk_env_u64(const char *v, uint64_t dflt)
-{
-    if (!v || !*v) return dflt;
-    char *end = nullptr;
-    const unsigned long long x = strtoull(v, &end, 10);
-    return (end && *end == 0) ? (uint64_t)x : dflt;
-}
-
-void mk_require_device(int device, const char *what)
-{
-    int cur = -1;
-    SW_HIP(hipGetDevice(&cur));
-    if (cur != device)
-        raise(SW_ERR_VALUE, "%s lives on device %d but the calling thread's current device is %d (sw_set_device)", what, device, cur);
-}
-
 // first occurrence in [lo, hi) whose record is >= rec
 __device__ inline uint64_t lb_rec(const sw_kmer *km, uint64_t lo, uint64_t hi, uint32_t rec)
 {
@@ -554,9 +538,9 @@ void run_markers(const sw_kmer *kmers, uint64_t n_kmers, const sw_node *nodes, u
         if (h[0] <= h[1] && (h[0] < ro_host[0] || h[1] >= ro_host[n_asm]))
             raise(SW_ERR_VALUE, "record_offsets [%u, %u) do not cover the index's records %u .. %u", ro_host[0], ro_host[n_asm], h[0], h[1]);
     }
-    const uint32_t loc_cap = (uint32_t)std::min<uint64_t>(std::max<uint64_t>(mk_env_u64(SW_TEST_GETENV("SEQWIN_AMD_LOC_LDS_CAP"), MK_LOC_CAP), 1), MK_LOC_CAP);
-    const uint32_t vote_cap = (uint32_t)std::min<uint64_t>(std::max<uint64_t>(mk_env_u64(SW_TEST_GETENV("SEQWIN_AMD_LOC_VOTE_CAP"), MK_VOTE_CAP), 1), MK_VOTE_CAP);
-    const uint64_t fp_bits = std::min<uint64_t>(mk_env_u64(SW_TEST_GETENV("SEQWIN_AMD_LOC_FP_BITS"), 64), 64);
+    const uint32_t loc_cap = (uint32_t)std::min<uint64_t>(std::max<uint64_t>(env_u64(SW_TEST_GETENV("SEQWIN_AMD_LOC_LDS_CAP"), MK_LOC_CAP), 1), MK_LOC_CAP);
+    const uint32_t vote_cap = (uint32_t)std::min<uint64_t>(std::max<uint64_t>(env_u64(SW_TEST_GETENV("SEQWIN_AMD_LOC_VOTE_CAP"), MK_VOTE_CAP), 1), MK_VOTE_CAP);
+    const uint64_t fp_bits = std::min<uint64_t>(env_u64(SW_TEST_GETENV("SEQWIN_AMD_LOC_FP_BITS"), 64), 64);
     const uint64_t fp_mask = fp_bits >= 64 ? ~0ull : (1ull << fp_bits) - 1;
     Core g{kmers, nodes, sg_off, sg_rank, d_ro.p, n_asm, n_sg};
 
@@ -674,7 +658,7 @@ int sw_index_marker_locs(const sw_index *kept, const sw_subgraphs *sg, const uin
     return guarded([&] {
         if (!kept || !sg || !out) raise(SW_ERR_VALUE, "markers: a NULL handle");
         check_args(record_offsets, n_assemblies, n_tar, windowsize);
-        mk_require_device(kept->device, "the index");
+        require_device(kept->device, "the index");
         int sg_dev = 0;
         uint64_t n_sg = 0, n_out = 0;
         const uint64_t *offs = nullptr, *hashes = nullptr;
@@ -753,7 +737,7 @@ int sw_markers_sizes(const sw_markers *m, uint64_t *n_sg, uint64_t *n_rep_kmers,
 int sw_markers_export(const sw_markers *m, sw_marker_rep *reps, uint64_t *rep_offsets, uint64_t *rep_hashes)
 {
     return guarded([&] {
-        mk_require_device(m->device, "the markers");
+        require_device(m->device, "the markers");
         struct { void *dst; const void *src; uint64_t bytes; } c[3] = {{reps, m->reps.p, m->n_sg * sizeof(sw_marker_rep)},
                                                                        {rep_offsets, m->rep_off.p, (m->n_sg + 1) * 8},
                                                                        {rep_hashes, m->rep_hashes.p, m->n_rep_kmers * 8}};
@@ -766,7 +750,7 @@ int sw_markers_export_rows(const sw_markers *m, uint64_t *row_offsets, sw_marker
 {
     return guarded([&] {
         if (!m->keep_rows) raise(SW_ERR_VALUE, "the rows were not kept (keep_rows = 0)");
-        mk_require_device(m->device, "the markers");
+        require_device(m->device, "the markers");
         struct { void *dst; const void *src; uint64_t bytes; } c[4] = {{row_offsets, m->row_off.p, (m->n_sg + 1) * 8},
                                                                        {rows, m->rows.p, m->n_rows * sizeof(sw_marker_row)},
                                                                        {kmer_offsets, m->kmer_off.p, (m->n_rows + 1) * 8},

@@ -5,9 +5,10 @@
 // The specification followed is Mash 2.x at its defaults, as DESIGN.md section 3 states it; tests/tools/minhash_host.py is its
 // host restatement.  Agreement with the `mash` binary itself has never been observed.
 //
-//   k_mh_hash     one pass over the packed words: a lane holds MH_L consecutive k-mers of one valid run, rolls the forward and the
-//                 reverse-complement word in registers, expands the canonical one to its ASCII bytes and runs MurmurHash3_x64_128
-//                 on them; hashes at or below the assembly's threshold are appended to its candidate range (one atomic per wave)
+//   k_mh_hash     one pass over the packed words by the batch's run / tile / lane walk (kmer_walk.hpp): a lane holds MH_L consecutive
+//                 k-mers of one valid run, expands the canonical one of every pair of rolled words to its ASCII bytes and runs
+//                 MurmurHash3_x64_128 on them; hashes at or below the assembly's threshold are appended to its candidate range
+//                 (one atomic per wave)
 //   k_mh_select   one workgroup per assembly: bitonic sort of the candidates in LDS, duplicates dropped, the S smallest kept
 //   general route an assembly that fell short (fewer than S distinct candidates under a threshold below the whole range, or more
 //                 candidates than the range holds) is finished exactly, once: all its k-mers hashed into a scratch, sorted by the
@@ -20,42 +21,19 @@
 #include <cmath>
 #include <memory>
 
-#include "device.hpp"
+#include "kmer_walk.hpp"
 
 namespace sw {
 namespace {
 
-constexpr uint32_t MH_TPB = 256, MH_WAVE = 64;
-constexpr uint32_t MH_L = 16;                       // consecutive k-mers per lane
-constexpr uint32_t MH_TILE = MH_WAVE * MH_L;        // k-mers per wave: one tile lies inside one valid run
+constexpr uint32_t MH_TPB = KW_TPB, MH_WAVE = KW_WAVE, MH_TILE = KW_TILE, MH_MAX_BLOCKS = KW_MAX_BLOCKS;   // (kmer_walk.hpp)
 constexpr uint32_t MH_SEL_MAX = 16384;              // most candidates a workgroup sorts in LDS (128 KiB of 64-bit values)
-constexpr uint32_t MH_MAX_BLOCKS = 1u << 22;         // workgroups per launch: 2^30 threads, below the 2^32 a launch may hold
 constexpr uint32_t MH_PAIR_COLS = 64;               // column sketches per workgroup of k_mh_pairs (16 per wave)
 constexpr uint32_t MH_PAIR_LDS_BYTES = 48 * 1024;   // a longer row sketch is searched in global memory
 constexpr uint64_t MM_C1 = 0x87c37b91114253d5ULL, MM_C2 = 0x4cf5ad432745937fULL;
 
-uint64_t mh_env_u64(const char *v, uint64_t dflt)
-{
-    if (!v || !*v) return dflt;
-    char *end = nullptr;
-    const unsigned long long x = strtoull(v, &end, 10);
-    return (end && *end == 0) ? (uint64_t)x : dflt;
-}
-
-// workgroups per launch of the hash pass and of the pair kernel.  SEQWIN_AMD_MH_MAX_BLOCKS (test library) lowers it, so that a small
-// batch or block needs several launches -- what the 15 000-genome set needs by its size.
-uint32_t mh_launch_blocks()
-{
-    return (uint32_t)std::max<uint64_t>(std::min<uint64_t>(mh_env_u64(SW_TEST_GETENV("SEQWIN_AMD_MH_MAX_BLOCKS"), MH_MAX_BLOCKS), MH_MAX_BLOCKS), 1);
-}
-
-void mh_require_device(int device, const char *what)
-{
-    int cur = -1;
-    SW_HIP(hipGetDevice(&cur));
-    if (cur != device)
-        raise(SW_ERR_VALUE, "%s lives on device %d but the calling thread's current device is %d (sw_set_device)", what, device, cur);
-}
+// workgroups per launch of the hash pass and of the pair kernel: launch_blocks(MH_BLOCKS_ENV); the switch (test library) lowers it
+constexpr const char *MH_BLOCKS_ENV = "SEQWIN_AMD_MH_MAX_BLOCKS";
 
 __device__ __forceinline__ uint64_t rotl64(uint64_t x, int r) { return (x << r) | (x >> (64 - r)); }
 
@@ -114,13 +92,7 @@ template <int NB> __device__ __forceinline__ uint64_t mm3_h1(uint64_t cl, uint32
 }
 
 struct HashArgs {
-    const uint32_t *packed;          // 16 bases per word, base i in bits [2 (i % 16), +2)
-    const uint64_t *run_base;        // [n_runs] batch-wide index of the run's first base
-    const uint32_t *run_nk;          // [n_runs] k-mers of the run (>= 1)
-    const uint32_t *run_asm;         // [n_runs]
-    const uint32_t *run_tile_off;    // [n_runs + 1] first tile of the run
-    uint32_t n_runs;
-    uint32_t tile_begin, tile_end;   // the tiles of this launch
+    RunView v;
     const uint64_t *thr;             // [n_asm] a hash <= thr[a] is a candidate (single: every hash is)
     unsigned long long *cnt;         // [n_asm] candidates seen (single: one counter)
     uint64_t *cand;                  // assembly a's range: cand[a * cap, (a + 1) * cap) (single: cand[0, cap))
@@ -134,41 +106,22 @@ template <int NB> __global__ __launch_bounds__(MH_TPB) void k_mh_hash(HashArgs g
 {
     __shared__ uint64_t stash[MH_TPB / MH_WAVE][MH_TILE];   // a lane's i-th candidate at [i * 64 + lane]
     const uint32_t wave = threadIdx.x / MH_WAVE, lane = threadIdx.x % MH_WAVE;
-    const uint64_t tile64 = (uint64_t)g.tile_begin + (uint64_t)blockIdx.x * (MH_TPB / MH_WAVE) + wave;
-    if (tile64 >= g.tile_end) return;   // (the whole wave)
-    const uint32_t tile = (uint32_t)tile64;
-    uint32_t lo = 0, hi = g.n_runs;     // the last run whose first tile is <= tile
-    while (lo + 1 < hi) {
-        const uint32_t mid = (lo + hi) >> 1;
-        if (g.run_tile_off[mid] <= tile) lo = mid; else hi = mid;
-    }
-    const uint32_t r = lo, nk = g.run_nk[r], a = g.run_asm[r];
-    const uint64_t first = (uint64_t)(tile - g.run_tile_off[r]) * MH_TILE + (uint64_t)lane * MH_L;
-    const uint32_t n_mine = first < nk ? (uint32_t)(nk - first < MH_L ? nk - first : MH_L) : 0;
+    uint32_t r, n_mine;
+    uint64_t first;
+    if (!wave_tile(g.v, lane, r, first, n_mine)) return;   // (the whole wave)
+    const uint32_t a = g.v.run_asm[r];
     const uint64_t T = g.single ? ~0ull : g.thr[a];
     const uint32_t k = g.k;
-    const uint64_t mask = k >= 32 ? ~0ull : (1ull << (2 * k)) - 1;
-    const uint32_t sh = 2 * (k - 1);
     uint32_t n_out = 0;
+    KmerRoller R(g.v.packed, k);
     if (n_mine) {
-        // the lane reads bases [pos, pos + k - 1 + n_mine), all inside the run
-        uint64_t pos = g.run_base[r] + first, fwd = 0, rev = 0;
-        uint32_t w = g.packed[pos >> 4] >> (2 * (uint32_t)(pos & 15)), left = 16 - (uint32_t)(pos & 15);
+        R.start(g.v.run_base[r] + first);
         const uint32_t nb = k - 1 + n_mine;
         for (uint32_t i = 0; i < nb; ++i) {
-            if (left == 0) {
-                w = g.packed[pos >> 4];
-                left = 16;
-            }
-            const uint64_t c = w & 3u;
-            w >>= 2;
-            --left;
-            ++pos;
-            fwd = ((fwd << 2) | c) & mask;          // first base most significant: integer order = byte-string order (A < C < G < T)
-            rev = (rev >> 2) | ((3 - c) << sh);
+            R.roll();
             if (i + 1 >= k) {
                 // the canonical k-mer with its first base LOWEST is the complement of the other strand's word
-                const uint64_t cl = ~(fwd > rev ? fwd : rev) & mask;
+                const uint64_t cl = ~(R.fwd > R.rev ? R.fwd : R.rev) & R.mask;
                 uint64_t h = mm3_h1<NB>(cl, k, g.seed, g.m1, g.m2);
                 if (g.bits32) h &= 0xFFFFFFFFull;
                 if (h <= T) {
@@ -178,17 +131,9 @@ template <int NB> __global__ __launch_bounds__(MH_TPB) void k_mh_hash(HashArgs g
             }
         }
     }
-    uint32_t incl = n_out;
-    for (uint32_t d = 1; d < MH_WAVE; d <<= 1) {
-        const uint32_t v = __shfl_up(incl, d, MH_WAVE);
-        if (lane >= d) incl += v;
-    }
-    const uint32_t total = __shfl(incl, MH_WAVE - 1, MH_WAVE);
-    if (total == 0) return;
-    unsigned long long base = 0;
-    if (lane == 0) base = atomicAdd(g.cnt + (g.single ? 0 : a), (unsigned long long)total);   // one atomic per wave
-    base = __shfl(base, 0, MH_WAVE);
-    const uint64_t at = base + (incl - n_out);
+    const WaveRange w = wave_append(g.cnt + (g.single ? 0 : a), lane, n_out);   // one atomic per wave
+    if (w.total == 0) return;
+    const uint64_t at = w.base + w.offset;
     uint64_t *dst = g.cand + (g.single ? 0 : (uint64_t)a * g.cap);
     for (uint32_t i = 0; i < n_out; ++i)
         if (at + i < g.cap) dst[at + i] = stash[wave][i * MH_WAVE + lane];   // a count beyond the capacity is recorded, not written
@@ -390,26 +335,13 @@ struct sw_minhash {
 namespace sw {
 namespace {
 
-template <int NB> void launch_hash(const HashArgs &g, hipStream_t stream)
-{
-    // a launch holds fewer than 2^32 threads (more wrap silently: the 15 000-genome set has 73 M tiles): MH_MAX_BLOCKS per launch
-    const uint64_t per = MH_TPB / MH_WAVE, end = g.tile_end, step = (uint64_t)mh_launch_blocks() * per;
-    for (uint64_t t0 = g.tile_begin; t0 < end; t0 += step) {
-        HashArgs part = g;
-        part.tile_begin = (uint32_t)t0;
-        part.tile_end = (uint32_t)std::min<uint64_t>(end, t0 + step);
-        const uint64_t tiles = (uint64_t)part.tile_end - part.tile_begin;
-        hipLaunchKernelGGL(k_mh_hash<NB>, dim3((unsigned)((tiles + per - 1) / per)), dim3(MH_TPB), 0, stream, part);
-        SW_HIP(hipGetLastError());
-    }
-}
-
 void run_hash(const HashArgs &g, hipStream_t stream)
 {
+    const uint32_t blocks = launch_blocks(MH_BLOCKS_ENV);
     switch (g.k / 16) {
-    case 0: launch_hash<0>(g, stream); break;
-    case 1: launch_hash<1>(g, stream); break;
-    default: launch_hash<2>(g, stream); break;
+    case 0: launch_tiles(k_mh_hash<0>, g, blocks, stream); break;
+    case 1: launch_tiles(k_mh_hash<1>, g, blocks, stream); break;
+    default: launch_tiles(k_mh_hash<2>, g, blocks, stream); break;
     }
 }
 
@@ -430,30 +362,12 @@ void batch_minhash(const sw_batch &b, uint32_t k, uint64_t S, uint32_t seed, hip
     if (n_asm > MH_MAX_BLOCKS) raise(SW_ERR_VALUE, "minhash: %llu assemblies exceed one launch (%u)", (unsigned long long)n_asm, MH_MAX_BLOCKS);
     if (R && !b.d_packed.p) raise(SW_ERR_VALUE, "minhash: the batch holds no packed bases (it must be resident)");
     const bool bits32 = k <= 16;
-    // ---- the valid runs of length >= k, once per call (as get_plan takes its segments) ----
-    std::vector<uint64_t> run_base;
-    std::vector<uint32_t> run_nk, run_asm, run_tile_off, asm_tile_off(n_asm + 1, 0);
-    std::vector<uint64_t> n_valid(n_asm, 0);
-    uint64_t tiles = 0;
-    for (uint64_t a = 0; a < n_asm; ++a) {
-        asm_tile_off[a] = (uint32_t)tiles;
-        for (uint32_t r = h.record_offsets[a]; r < h.record_offsets[a + 1]; ++r)
-            for (uint32_t q = h.rec_run_off[r]; q < h.rec_run_off[r + 1]; ++q) {
-                if (h.run_len[q] < k) continue;
-                const uint32_t nk = h.run_len[q] - k + 1;
-                run_base.push_back(h.rec_base[r] + h.run_pos[q]);
-                run_nk.push_back(nk);
-                run_asm.push_back((uint32_t)a);
-                run_tile_off.push_back((uint32_t)tiles);
-                tiles += ((uint64_t)nk + MH_TILE - 1) / MH_TILE;
-                n_valid[a] += nk;
-                if (tiles >= 0xFFFFFFFFull) raise(SW_ERR_RUNTIME, "minhash: the batch has more k-mers than one call takes (2^32 tiles of %u)", MH_TILE);
-            }
-    }
-    asm_tile_off[n_asm] = (uint32_t)tiles;
-    run_tile_off.push_back((uint32_t)tiles);
-    const uint64_t n_runs = run_nk.size();
-    if (n_runs >= 0xFFFFFFFFull) raise(SW_ERR_RUNTIME, "minhash: %llu valid runs exceed 32-bit indices", (unsigned long long)n_runs);
+    // ---- the valid runs of length >= k, once per call (kmer_walk.hpp) ----
+    RunTiles RT;
+    build_run_tiles(h, k, "minhash", RT);
+    const std::vector<uint32_t> &asm_tile_off = RT.asm_tile_off;
+    const uint64_t n_runs = RT.n_runs;
+    auto n_valid = [&](uint64_t a) { return RT.asm_kmers[a + 1] - RT.asm_kmers[a]; };
 
     // ---- thresholds.  An assembly keeps the hashes at or below T_a = lambda / n_valid_a of the hash range, lambda = 2 S + 256
     // expected candidates (the multiple 2, the floor 256: small S stays far from falling short); a range holds `cap` of them.
@@ -463,32 +377,29 @@ void batch_minhash(const sw_batch &b, uint32_t k, uint64_t S, uint32_t seed, hip
     while ((double)cap < lambda + 8.0 * std::sqrt(lambda)) cap <<= 1;
     const bool lds_route = cap <= MH_SEL_MAX && n_runs > 0;   // a larger S: every assembly by the general route
     cap = std::min<uint64_t>(cap, MH_SEL_MAX);
-    cap = std::max<uint64_t>(std::min<uint64_t>(cap, mh_env_u64(SW_TEST_GETENV("SEQWIN_AMD_MH_CAND_CAP"), cap)), 1);
+    cap = std::max<uint64_t>(std::min<uint64_t>(cap, env_u64(SW_TEST_GETENV("SEQWIN_AMD_MH_CAND_CAP"), cap)), 1);
     uint32_t P = 1;
     while (P < cap) P <<= 1;
     std::vector<uint64_t> thr(n_asm), ub_off(n_asm + 1, 0);
     std::vector<uint8_t> whole(n_asm);
     const double range = bits32 ? 4294967296.0 : 18446744073709551616.0;
     for (uint64_t a = 0; a < n_asm; ++a) {
-        const double frac = n_valid[a] ? lambda / (double)n_valid[a] : 1.0;
+        const double frac = n_valid(a) ? lambda / (double)n_valid(a) : 1.0;
         whole[a] = frac >= 1.0;
         thr[a] = whole[a] ? ~0ull : (uint64_t)(frac * range);
-        ub_off[a + 1] = ub_off[a] + std::min<uint64_t>(S, n_valid[a]);
+        ub_off[a + 1] = ub_off[a] + std::min<uint64_t>(S, n_valid(a));
     }
 
     Event e0, e1, e2;
     SW_HIP(hipEventRecord(e0, stream));
-    DevArray<uint64_t> d_run_base(n_runs), d_thr(n_asm), d_ub(n_asm + 1), d_tmp(ub_off[n_asm]);
-    DevArray<uint32_t> d_run_nk(n_runs), d_run_asm(n_runs), d_run_tile(n_runs + 1), d_len(n_asm);
+    DevRunTiles runs(RT, b.d_packed.p, stream);
+    DevArray<uint64_t> d_thr(n_asm), d_ub(n_asm + 1), d_tmp(ub_off[n_asm]);
+    DevArray<uint32_t> d_len(n_asm);
     DevArray<uint8_t> d_whole(n_asm), d_fall(n_asm);
     DevArray<unsigned long long> d_cnt(n_asm + 1);   // [n_asm]: the general route's counter
     auto up = [&](void *dst, const void *src, size_t bytes) {
         if (bytes) SW_HIP(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, stream));
     };
-    up(d_run_base.p, run_base.data(), n_runs * 8);
-    up(d_run_nk.p, run_nk.data(), n_runs * 4);
-    up(d_run_asm.p, run_asm.data(), n_runs * 4);
-    up(d_run_tile.p, run_tile_off.data(), (n_runs + 1) * 4);
     up(d_thr.p, thr.data(), n_asm * 8);
     up(d_ub.p, ub_off.data(), (n_asm + 1) * 8);
     up(d_whole.p, whole.data(), n_asm);
@@ -496,12 +407,6 @@ void batch_minhash(const sw_batch &b, uint32_t k, uint64_t S, uint32_t seed, hip
     if (n_asm) SW_HIP(hipMemsetAsync(d_len.p, 0, n_asm * 4, stream));
     const uint32_t tl = k & 15u;
     HashArgs g{};
-    g.packed = b.d_packed.p;
-    g.run_base = d_run_base.p;
-    g.run_nk = d_run_nk.p;
-    g.run_asm = d_run_asm.p;
-    g.run_tile_off = d_run_tile.p;
-    g.n_runs = (uint32_t)n_runs;
     g.thr = d_thr.p;
     g.k = k;
     g.seed = seed;
@@ -513,8 +418,7 @@ void batch_minhash(const sw_batch &b, uint32_t k, uint64_t S, uint32_t seed, hip
     std::vector<unsigned long long> cnt(n_asm, 0);
     if (lds_route && n_asm) {
         DevArray<uint64_t> d_cand(n_asm * cap);
-        g.tile_begin = 0;
-        g.tile_end = (uint32_t)tiles;
+        g.v = runs.view(0, (uint32_t)RT.tiles);
         g.cnt = d_cnt.p;
         g.cand = d_cand.p;
         g.cap = cap;
@@ -536,15 +440,14 @@ void batch_minhash(const sw_batch &b, uint32_t k, uint64_t S, uint32_t seed, hip
     uint64_t n_general = 0;
     for (uint64_t a = 0; a < n_asm; ++a) {
         if (!fall[a]) continue;
-        const uint64_t nv = n_valid[a];
+        const uint64_t nv = n_valid(a);
         if (nv == 0) continue;   // (no k-mer: an empty sketch, d_len[a] = 0)
         ++n_general;
         DevArray<uint64_t> keys(nv), alt(nv);
         DevArray<uint32_t> d_fail(1);
         SW_HIP(hipMemsetAsync(d_cnt.p + n_asm, 0, 8, stream));
         SW_HIP(hipMemsetAsync(d_fail.p, 0, 4, stream));
-        g.tile_begin = asm_tile_off[a];
-        g.tile_end = asm_tile_off[a + 1];
+        g.v = runs.view(asm_tile_off[a], asm_tile_off[a + 1]);
         g.cnt = d_cnt.p + n_asm;
         g.cand = keys.p;
         g.cap = nv;
@@ -614,7 +517,7 @@ void device_counts(const sw_minhash &h, uint64_t r0, uint64_t r1, uint64_t c0, u
     const size_t esz = h.hash_bits == 32 ? 4 : 8, row_bytes = h.max_len * esz;
     const bool in_lds = row_bytes <= MH_PAIR_LDS_BYTES;
     const size_t lds = in_lds ? std::max<size_t>(row_bytes, 8) : 8;
-    const uint64_t rows_per = std::max<uint64_t>(mh_launch_blocks() / col_tiles, 1);   // (col_tiles < 2^26: below 2^32 threads either way)
+    const uint64_t rows_per = std::max<uint64_t>(launch_blocks(MH_BLOCKS_ENV) / col_tiles, 1);   // (col_tiles < 2^26: below 2^32 threads either way)
     for (uint64_t ra = 0; ra < nr; ra += rows_per) {
         const uint64_t rn = std::min<uint64_t>(rows_per, nr - ra);
         const dim3 grid((unsigned)(rn * col_tiles)), block(MH_TPB);
@@ -648,7 +551,7 @@ int sw_batch_minhash(const sw_batch *batch, uint64_t k, uint64_t s, uint64_t see
     return guarded([&] {
         check_k_s(k, s, seed);
         if (!batch || !out) raise(SW_ERR_VALUE, "minhash: a NULL handle");
-        mh_require_device(batch->device, "the batch");
+        require_device(batch->device, "the batch");
         StreamScope scope((hipStream_t)stream);
         std::unique_ptr<sw_minhash> o(new sw_minhash);
         o->device = batch->device;
@@ -723,7 +626,7 @@ int sw_minhash_export(const sw_minhash *h, uint64_t *offsets, uint64_t *hashes)
         if (!h) raise(SW_ERR_VALUE, "minhash: a NULL handle");
         if (offsets) memcpy(offsets, h->off_host.data(), (h->n + 1) * 8);
         if (!hashes || !h->n_hashes) return;
-        mh_require_device(h->device, "the sketches");
+        require_device(h->device, "the sketches");
         if (h->hash_bits == 32) {
             std::vector<uint32_t> h32(h->n_hashes);
             SW_HIP(hipMemcpy(h32.data(), h->h32.p, h->n_hashes * 4, hipMemcpyDeviceToHost));
@@ -741,7 +644,7 @@ int sw_minhash_counts(const sw_minhash *h, uint64_t r0, uint64_t r1, uint64_t c0
         const uint64_t np = (r1 - r0) * (c1 - c0);
         if (!np) return;
         if (!shared || !total) raise(SW_ERR_VALUE, "minhash: a NULL array");
-        mh_require_device(h->device, "the sketches");
+        require_device(h->device, "the sketches");
         DevArray<uint32_t> d_sh(np), d_to(np);
         device_counts(*h, r0, r1, c0, c1, d_sh.p, d_to.p, 0);
         SW_HIP(hipMemcpy(shared, d_sh.p, np * 4, hipMemcpyDeviceToHost));
@@ -761,7 +664,7 @@ int sw_minhash_frac_rowsums(const sw_minhash *h, uint64_t r0, uint64_t r1, uint6
             for (uint64_t r = 0; r < nr; ++r) rowsums[r] = 0.0;
             return;
         }
-        mh_require_device(h->device, "the sketches");
+        require_device(h->device, "the sketches");
         DevArray<uint32_t> d_sh(nr * nc), d_to(nr * nc), d_zero(1);
         DevArray<double> d_sum(nr);
         SW_HIP(hipMemsetAsync(d_zero.p, 0, 4, 0));

@@ -11,7 +11,7 @@
 //                  the distinct words numbered in order of first appearance in the query text (k_scr_first: atomicMin of the
 //                  position per word; flag and scan), the table's slots relabelled to those numbers; per query the list of
 //                  (bitmap word, mask) pairs that cover its k-mers (sort of query << 32 | number, k_scr_pairs)
-//   k_scr_probe    the hot path.  The run / tile / lane walk of k_mh_hash (minhash.hip): a tile of 1024 k-mers of one valid run per
+//   k_scr_probe    the hot path.  The batch's run / tile / lane walk (kmer_walk.hpp): a tile of 1024 k-mers of one valid run per
 //                  wave, 16 consecutive k-mers per lane.  A lane rolls its 16 canonical words, issues their 16 first-slot loads
 //                  together, resolves the occupied ones, and sets bit `number` of its assembly's row of a presence bitmap with
 //                  atomicOr -- consecutive hits that fall into one bitmap word leave as one atomic
@@ -24,13 +24,7 @@ namespace {
 
 // ---- probe ----------------------------------------------------------------------------------------------------------------------
 struct ProbeArgs {
-    const uint32_t *packed;          // 16 bases per word, base i in bits [2 (i % 16), +2)
-    const uint64_t *run_base;        // [n_runs] batch-wide index of the run's first base
-    const uint32_t *run_nk;          // [n_runs] k-mers of the run (>= 1)
-    const uint32_t *run_asm;         // [n_runs]
-    const uint32_t *run_tile_off;    // [n_runs + 1] first tile of the run
-    uint32_t n_runs;
-    uint32_t tile_begin, tile_end;   // the tiles of this launch: all of assemblies [asm0, asm0 + rows of the bitmap)
+    RunView v;                       // the tiles of this launch: all of assemblies [asm0, asm0 + rows of the bitmap)
     Table t;                         // slots hold number + 1, keys are in number order
     uint32_t *bitmap;                // [assembly - asm0][words]
     uint32_t asm0;
@@ -41,47 +35,24 @@ struct ProbeArgs {
 
 __global__ __launch_bounds__(SCR_TPB) void k_scr_probe(ProbeArgs g)
 {
-    const uint32_t wave = threadIdx.x / SCR_WAVE, lane = threadIdx.x % SCR_WAVE;
-    const uint64_t tile64 = (uint64_t)g.tile_begin + (uint64_t)blockIdx.x * SCR_WPB + wave;
-    if (tile64 >= g.tile_end) return;   // (the whole wave)
-    const uint32_t tile = (uint32_t)tile64;
-    uint32_t lo = 0, hi = g.n_runs;     // the last run whose first tile is <= tile
-    while (lo + 1 < hi) {
-        const uint32_t mid = (lo + hi) >> 1;
-        if (g.run_tile_off[mid] <= tile) lo = mid; else hi = mid;
-    }
-    const uint32_t r = lo, nk = g.run_nk[r], a = g.run_asm[r];
-    const uint64_t first = (uint64_t)(tile - g.run_tile_off[r]) * SCR_TILE + (uint64_t)lane * SCR_L;
-    const uint32_t n_mine = first < nk ? (uint32_t)(nk - first < SCR_L ? nk - first : SCR_L) : 0;
-    const uint32_t k = g.k;
-    const uint64_t mask = k >= 32 ? ~0ull : (1ull << (2 * k)) - 1;
-    const uint32_t sh = 2 * (k - 1);
+    const uint32_t lane = threadIdx.x % SCR_WAVE;
+    uint32_t r, n_mine;
+    uint64_t first;
+    if (!wave_tile(g.v, lane, r, first, n_mine)) return;   // (the whole wave)
+    const uint32_t a = g.v.run_asm[r], k = g.k;
     unsigned long long hits = 0, atomics = 0;
+    KmerRoller R(g.v.packed, k);
     if (n_mine) {
-        // the lane reads bases [pos, pos + k - 1 + n_mine), all inside the run
-        uint64_t pos = g.run_base[r] + first, fwd = 0, rev = 0;
-        uint32_t w = g.packed[pos >> 4] >> (2 * (uint32_t)(pos & 15)), left = 16 - (uint32_t)(pos & 15);
-        auto roll = [&]() {
-            if (left == 0) {
-                w = g.packed[pos >> 4];
-                left = 16;
-            }
-            const uint64_t c = w & 3u;
-            w >>= 2;
-            --left;
-            ++pos;
-            fwd = ((fwd << 2) | c) & mask;
-            rev = (rev >> 2) | ((3 - c) << sh);
-        };
-        for (uint32_t i = 0; i + 1 < k; ++i) roll();
+        R.start(g.v.run_base[r] + first);
+        for (uint32_t i = 0; i + 1 < k; ++i) R.roll();
         uint64_t canon[SCR_L];
         uint32_t home[SCR_L], slot[SCR_L];
 #pragma unroll
         for (uint32_t j = 0; j < SCR_L; ++j) {
             canon[j] = 0;
             if (j < n_mine) {
-                roll();
-                canon[j] = fwd < rev ? fwd : rev;
+                R.roll();
+                canon[j] = R.fwd < R.rev ? R.fwd : R.rev;
             }
         }
 #pragma unroll
@@ -211,12 +182,11 @@ void batch_screen(const sw_batch &b, const uint64_t *offsets, const char *blob, 
     o.n_distinct = n_distinct;
     SW_HIP(hipEventRecord(e1, stream));
 
-    // ---- the valid runs of length >= k, once per call (screen_core.hpp) ----
+    // ---- the valid runs of length >= k, once per call (kmer_walk.hpp) ----
     RunTiles T;
-    build_run_tiles(h, k, T);
-    const std::vector<uint64_t> &run_base = T.run_base, &asm_kmers = T.asm_kmers;
-    const std::vector<uint32_t> &run_nk = T.run_nk, &run_asm = T.run_asm, &run_tile_off = T.run_tile_off, &asm_tile_off = T.asm_tile_off;
-    const uint64_t n_runs = T.n_runs;
+    build_run_tiles(h, k, "screen", T);
+    const std::vector<uint64_t> &asm_kmers = T.asm_kmers;
+    const std::vector<uint32_t> &asm_tile_off = T.asm_tile_off;
 
     // ---- probe and reduce, a chunk of assemblies at a time ----
     uint64_t probed = 0, launches = 0, chunks = 0;
@@ -226,44 +196,28 @@ void batch_screen(const sw_batch &b, const uint64_t *offsets, const char *blob, 
         const uint64_t words = (n_distinct + 31) / 32;
         // the bitmap's budget changes speed only; 1 GiB has no measurement behind it.  SEQWIN_AMD_SCR_BITMAP_KB (test library) sets it
         uint64_t budget = SCR_BITMAP_BYTES;
-        if (const char *e = SW_TEST_GETENV("SEQWIN_AMD_SCR_BITMAP_KB")) budget = scr_env_u64(e, budget >> 10) << 10;
+        if (const char *e = SW_TEST_GETENV("SEQWIN_AMD_SCR_BITMAP_KB")) budget = env_u64(e, budget >> 10) << 10;
         const uint64_t rows_max = std::min<uint64_t>(std::max<uint64_t>(budget / (words * 4), 1), n_asm);
         DevArray<uint32_t> bitmap(rows_max * words);
-        DevArray<uint64_t> d_run_base(n_runs);
-        DevArray<uint32_t> d_run_nk(n_runs), d_run_asm(n_runs), d_run_tile(n_runs + 1);
+        DevRunTiles runs(T, b.d_packed.p, stream);
         DevArray<unsigned long long> d_stat(2);
-        up(d_run_base.p, run_base.data(), n_runs * 8);
-        up(d_run_nk.p, run_nk.data(), n_runs * 4);
-        up(d_run_asm.p, run_asm.data(), n_runs * 4);
-        up(d_run_tile.p, run_tile_off.data(), (n_runs + 1) * 4);
         SW_HIP(hipMemsetAsync(d_stat.p, 0, 16, stream));
         SW_HIP(hipMemsetAsync(bitmap.p, 0, rows_max * words * 4, stream));
         ProbeArgs g{};
-        g.packed = b.d_packed.p;
-        g.run_base = d_run_base.p;
-        g.run_nk = d_run_nk.p;
-        g.run_asm = d_run_asm.p;
-        g.run_tile_off = d_run_tile.p;
-        g.n_runs = (uint32_t)n_runs;
         g.t = Table{slots.p, by_number.p, cap, bits};
         g.bitmap = bitmap.p;
         g.words = words;
         g.stat = d_stat.p;
         g.k = k;
-        const uint64_t blocks_max = scr_launch_blocks(), tile_step = blocks_max * SCR_WPB;
+        const uint32_t blocks_max = launch_blocks(SCR_BLOCKS_ENV);
         const uint32_t q_step = (uint32_t)std::max<uint64_t>(blocks_max / ((rows_max + SCR_RED_ROWS - 1) / SCR_RED_ROWS), 1);
         for (uint64_t a0 = 0; a0 < n_asm; a0 += rows_max, ++chunks) {
             const uint64_t a1 = std::min<uint64_t>(n_asm, a0 + rows_max), rows = a1 - a0;
             for (int i = 0; i < 3; ++i) ev.emplace_back(new Event);
             SW_HIP(hipEventRecord(*ev[3 * chunks], stream));
             g.asm0 = (uint32_t)a0;
-            for (uint64_t t0 = asm_tile_off[a0]; t0 < asm_tile_off[a1]; t0 += tile_step, ++launches) {
-                g.tile_begin = (uint32_t)t0;
-                g.tile_end = (uint32_t)std::min<uint64_t>(asm_tile_off[a1], t0 + tile_step);
-                const uint64_t n_tiles = (uint64_t)g.tile_end - g.tile_begin;
-                hipLaunchKernelGGL(k_scr_probe, dim3((unsigned)((n_tiles + SCR_WPB - 1) / SCR_WPB)), dim3(SCR_TPB), 0, stream, g);
-                SW_HIP(hipGetLastError());
-            }
+            g.v = runs.view(asm_tile_off[a0], asm_tile_off[a1]);
+            launches += launch_tiles(k_scr_probe, g, blocks_max, stream);
             probed += asm_kmers[a1] - asm_kmers[a0];
             SW_HIP(hipEventRecord(*ev[3 * chunks + 1], stream));
             const uint32_t row_tiles = (uint32_t)((rows + SCR_RED_ROWS - 1) / SCR_RED_ROWS);
@@ -307,17 +261,9 @@ int sw_batch_screen(const sw_batch *batch, const uint64_t *offsets, const char *
 {
     return guarded([&] {
         if (k < 1 || k > 32) raise(SW_ERR_VALUE, "screen: k-mer length must lie in 1..32 (got %llu)", (unsigned long long)k);
-        if (!batch || !out || (n_queries && !offsets)) raise(SW_ERR_VALUE, "screen: a NULL handle or array");
-        if (n_queries >= 0xFFFFFFFFull) raise(SW_ERR_VALUE, "screen: %llu queries exceed 32-bit indices", (unsigned long long)n_queries);
-        if (n_queries) {
-            if (offsets[0] != 0) raise(SW_ERR_VALUE, "screen: offsets must start at 0");
-            for (uint64_t q = 0; q < n_queries; ++q)
-                if (offsets[q] > offsets[q + 1]) raise(SW_ERR_VALUE, "screen: offsets must be non-decreasing (query %llu)", (unsigned long long)q);
-            if (offsets[n_queries] >= SCR_MAX_TEXT)
-                raise(SW_ERR_VALUE, "screen: %llu bytes of query text; fewer than 2^32 - 256 are taken", (unsigned long long)offsets[n_queries]);
-            if (offsets[n_queries] && !blob) raise(SW_ERR_VALUE, "screen: a NULL handle or array");
-        }
-        scr_require_device(batch->device, "the batch");
+        if (!batch || !out) raise(SW_ERR_VALUE, "screen: a NULL handle or array");
+        check_queries("screen", offsets, blob, n_queries);
+        require_device(batch->device, "the batch");
         StreamScope scope((hipStream_t)stream);
         std::unique_ptr<sw_screen> o(new sw_screen);
         o->device = batch->device;
@@ -355,7 +301,7 @@ int sw_screen_counts(const sw_screen *h, uint64_t r0, uint64_t r1, uint64_t c0, 
         const uint64_t nr = r1 - r0, nc = c1 - c0;
         if (!nr || !nc) return;
         if (!counts) raise(SW_ERR_VALUE, "screen: a NULL handle or array");
-        scr_require_device(h->device, "the screen");
+        require_device(h->device, "the screen");
         SW_HIP(hipMemcpy2D(counts, nc * 4, h->counts.p + r0 * h->n_asm + c0, h->n_asm * 4, nc * 4, nr, hipMemcpyDeviceToHost));
     });
 }

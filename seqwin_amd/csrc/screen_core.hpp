@@ -1,48 +1,40 @@
-// screen_core.hpp -- the query side of screen.hip, shared with hits.hip: the canonical words of the query text, the distinct words,
-// the open-addressing table over them and their numbers by first appearance; and the batch's valid runs cut into tiles of 1024
-// k-mers, as the probe kernels of both files walk them.  Device functions cannot be linked across translation units here, so
-// both files include this header.
+// screen_core.hpp -- the query side of screen.hip, shared with hits.hip: the check of the caller's queries, the canonical words of the
+// query text, the distinct words, the open-addressing table over them and their numbers by first appearance.  The batch side -- the
+// valid runs cut into tiles, the walk of the probe kernels of both files -- is kmer_walk.hpp.  Device functions cannot be linked
+// across translation units here, so both files include this header.
 #pragma once
 #include <cstring>  // rocprim's texture iterator needs ::memset declared first
 #include <memory>
 
 #include <rocprim/rocprim.hpp>
 
-#include "device.hpp"
+#include "kmer_walk.hpp"
 
 namespace sw {
 namespace {
 
-constexpr uint32_t SCR_TPB = 256, SCR_WAVE = 64, SCR_WPB = SCR_TPB / SCR_WAVE;
-constexpr uint32_t SCR_L = 16;                        // consecutive k-mers per lane
-constexpr uint32_t SCR_TILE = SCR_WAVE * SCR_L;       // k-mers per wave: one tile lies inside one valid run
-constexpr uint32_t SCR_MAX_BLOCKS = 1u << 22;         // workgroups per launch: 2^30 threads, below the 2^32 a launch may hold
+constexpr uint32_t SCR_TPB = KW_TPB, SCR_WAVE = KW_WAVE, SCR_WPB = KW_WPB, SCR_L = KW_L, SCR_MAX_BLOCKS = KW_MAX_BLOCKS;   // (kmer_walk.hpp)
 constexpr uint64_t SCR_MAX_TEXT = 0xFFFFFFFFull - 255; // query text: fewer bytes than this (a thread per byte in workgroups of 256)
 constexpr uint64_t SCR_MAX_DISTINCT = 1ull << 31;     // distinct query k-mers: fewer than this (a slot holds number + 1 in 32 bits)
 constexpr uint64_t SCR_BITMAP_BYTES = 1ull << 30;     // budget of the presence bitmap: speed only, chosen without a measurement
 constexpr uint32_t SCR_RED_ROWS = 64;                 // assemblies per workgroup of k_scr_reduce (16 per wave)
 constexpr uint32_t SCR_NONE = 0xFFFFFFFFu;
 
-uint64_t scr_env_u64(const char *v, uint64_t dflt)
-{
-    if (!v || !*v) return dflt;
-    char *end = nullptr;
-    const unsigned long long x = strtoull(v, &end, 10);
-    return (end && *end == 0) ? (uint64_t)x : dflt;
-}
+// workgroups per launch of the query side's kernels: launch_blocks(SCR_BLOCKS_ENV); the switch (test library) lowers it so that a
+// small input needs several launches
+constexpr const char *SCR_BLOCKS_ENV = "SEQWIN_AMD_SCR_MAX_BLOCKS";
 
-// workgroups per launch; SEQWIN_AMD_SCR_MAX_BLOCKS (test library) lowers it so that a small input needs several launches
-uint32_t scr_launch_blocks()
+// what a call says about its queries by itself; what: the caller's name in the messages
+void check_queries(const char *what, const uint64_t *offsets, const char *blob, uint64_t nq)
 {
-    return (uint32_t)std::max<uint64_t>(std::min<uint64_t>(scr_env_u64(SW_TEST_GETENV("SEQWIN_AMD_SCR_MAX_BLOCKS"), SCR_MAX_BLOCKS), SCR_MAX_BLOCKS), 1);
-}
-
-void scr_require_device(int device, const char *what)
-{
-    int cur = -1;
-    SW_HIP(hipGetDevice(&cur));
-    if (cur != device)
-        raise(SW_ERR_VALUE, "%s lives on device %d but the calling thread's current device is %d (sw_set_device)", what, device, cur);
+    if (nq && !offsets) raise(SW_ERR_VALUE, "%s: a NULL handle or array", what);
+    if (nq >= 0xFFFFFFFFull) raise(SW_ERR_VALUE, "%s: %llu queries exceed 32-bit indices", what, (unsigned long long)nq);
+    if (!nq) return;
+    if (offsets[0] != 0) raise(SW_ERR_VALUE, "%s: offsets must start at 0", what);
+    for (uint64_t q = 0; q < nq; ++q)
+        if (offsets[q] > offsets[q + 1]) raise(SW_ERR_VALUE, "%s: offsets must be non-decreasing (query %llu)", what, (unsigned long long)q);
+    if (offsets[nq] >= SCR_MAX_TEXT) raise(SW_ERR_VALUE, "%s: %llu bytes of query text; fewer than 2^32 - 256 are taken", what, (unsigned long long)offsets[nq]);
+    if (offsets[nq] && !blob) raise(SW_ERR_VALUE, "%s: a NULL handle or array", what);
 }
 
 // ---- the table ------------------------------------------------------------------------------------------------------------------
@@ -250,10 +242,10 @@ __global__ __launch_bounds__(SCR_TPB) void k_scr_pairs(uint64_t base, uint64_t e
     }
 }
 
-// kern(base, end, args ...) over [0, n) in launches of at most scr_launch_blocks() workgroups
+// kern(base, end, args ...) over [0, n) in launches of at most launch_blocks(SCR_BLOCKS_ENV) workgroups
 template <class K, class... A> void launch_1d(K kern, uint64_t n, hipStream_t stream, A... args)
 {
-    const uint64_t per = (uint64_t)scr_launch_blocks() * SCR_TPB;
+    const uint64_t per = (uint64_t)launch_blocks(SCR_BLOCKS_ENV) * SCR_TPB;
     for (uint64_t base = 0; base < n; base += per) {
         const uint64_t cnt = std::min<uint64_t>(per, n - base);
         hipLaunchKernelGGL(kern, dim3((unsigned)((cnt + SCR_TPB - 1) / SCR_TPB)), dim3(SCR_TPB), 0, stream, base, base + cnt, args...);
@@ -356,7 +348,7 @@ void build_query_side(const uint64_t *offsets, const char *blob, uint64_t nq, ui
     uint32_t bits = 0;
     while ((1ull << bits) < 2 * n_distinct) ++bits;
     if (const char *e = SW_TEST_GETENV("SEQWIN_AMD_SCR_TABLE_BITS")) {
-        const uint64_t want = scr_env_u64(e, bits);
+        const uint64_t want = env_u64(e, bits);
         if (want > 32 || (1ull << want) <= n_distinct)
             raise(SW_ERR_VALUE, "screen: a table of 2^%llu slots does not exceed the %llu distinct query k-mers", (unsigned long long)want,
                   (unsigned long long)n_distinct);
@@ -385,46 +377,6 @@ void build_query_side(const uint64_t *offsets, const char *blob, uint64_t nq, ui
     SW_HIP(hipMemcpyAsync(&Q.chain, Q.d_stat.p, 4, hipMemcpyDeviceToHost, stream));
     SW_HIP(hipStreamSynchronize(stream));
 }
-
-// ---- the valid runs of length >= k as tiles of SCR_TILE k-mers, once per call (as sw_batch_minhash takes them) ----------------------
-struct RunTiles {
-    std::vector<uint64_t> run_base;                 // batch-wide index of the run's first base
-    std::vector<uint32_t> run_nk, run_asm, run_tile_off, run_rec, run_pos, asm_tile_off;   // run_rec / run_pos: the record and the run's place in it
-    std::vector<uint64_t> asm_kmers;                // k-mers of the assemblies before a
-    uint64_t tiles = 0, n_runs = 0;
-};
-
-void build_run_tiles(const HostBatch &h, uint32_t k, RunTiles &T)
-{
-    const uint64_t n_asm = h.n_assemblies;
-    T.asm_tile_off.assign(n_asm + 1, 0);
-    T.asm_kmers.assign(n_asm + 1, 0);
-    uint64_t tiles = 0;
-    for (uint64_t a = 0; a < n_asm; ++a) {
-        T.asm_tile_off[a] = (uint32_t)tiles;
-        T.asm_kmers[a + 1] = T.asm_kmers[a];
-        for (uint32_t r = h.record_offsets[a]; r < h.record_offsets[a + 1]; ++r)
-            for (uint32_t q = h.rec_run_off[r]; q < h.rec_run_off[r + 1]; ++q) {
-                if (h.run_len[q] < k) continue;
-                const uint32_t nk = h.run_len[q] - k + 1;
-                T.run_base.push_back(h.rec_base[r] + h.run_pos[q]);
-                T.run_nk.push_back(nk);
-                T.run_asm.push_back((uint32_t)a);
-                T.run_rec.push_back(r);
-                T.run_pos.push_back(h.run_pos[q]);
-                T.run_tile_off.push_back((uint32_t)tiles);
-                tiles += ((uint64_t)nk + SCR_TILE - 1) / SCR_TILE;
-                T.asm_kmers[a + 1] += nk;
-                if (tiles >= 0xFFFFFFFFull) raise(SW_ERR_RUNTIME, "screen: the batch has more k-mers than one call takes (2^32 tiles of %u)", SCR_TILE);
-            }
-    }
-    T.asm_tile_off[n_asm] = (uint32_t)tiles;
-    T.run_tile_off.push_back((uint32_t)tiles);
-    T.tiles = tiles;
-    T.n_runs = T.run_nk.size();
-    if (T.n_runs >= 0xFFFFFFFFull) raise(SW_ERR_RUNTIME, "screen: %llu valid runs exceed 32-bit indices", (unsigned long long)T.n_runs);
-}
-
 
 }  // namespace
 }  // namespace sw

@@ -298,12 +298,12 @@ void fetch_device(const DevRuns &runs, const sw_interval *d_iv, uint64_t n, sw_s
         SW_HIP(hipMemcpy(&o.bytes, o.off.p + n, 8, hipMemcpyDeviceToHost));
     }
     o.blob.alloc(o.bytes);
-    // a launch holds at most sq_launch_blocks() workgroups (fewer than 2^32 threads) and SQ_PER_WAVE intervals per wave
-    const uint64_t per_launch = (uint64_t)sq_launch_blocks() * SQ_WPB * SQ_PER_WAVE;
+    // a launch holds at most launch_blocks(SQ_BLOCKS_ENV) workgroups (fewer than 2^32 threads) and SQ_PER_WAVE intervals per wave
+    const uint64_t per_launch = (uint64_t)launch_blocks(SQ_BLOCKS_ENV) * SQ_WPB * SQ_PER_WAVE;
     uint64_t launches = 0;
     for (uint64_t i0 = 0; i0 < n; i0 += per_launch, ++launches) {
         const uint64_t i1 = std::min<uint64_t>(n, i0 + per_launch);
-        const uint64_t blocks = std::min<uint64_t>(sq_launch_blocks(), (i1 - i0 + SQ_WPB - 1) / SQ_WPB);
+        const uint64_t blocks = std::min<uint64_t>(launch_blocks(SQ_BLOCKS_ENV), (i1 - i0 + SQ_WPB - 1) / SQ_WPB);
         hipLaunchKernelGGL(k_fetch, dim3((unsigned)blocks), dim3(SQ_TPB), 0, SQ_STREAM, runs.t, d_iv, o.off.p, i0, i1, o.blob.p, o.flags.p);
         SW_HIP(hipGetLastError());
     }
@@ -342,7 +342,7 @@ void distances_device(const DevRuns &runs, const sw_interval *d_R, const sw_inte
         a.S = d_S;
         a.dist = d_dist;
         a.strand = d_strand;
-        const uint64_t max_threads = (uint64_t)sq_launch_blocks() * SQ_TPB;
+        const uint64_t max_threads = (uint64_t)launch_blocks(SQ_BLOCKS_ENV) * SQ_TPB;
         for (uint32_t c = 0; c + 1 < ED_CLASSES; ++c) {   // register route, g = 2^c lanes per pair
             const uint64_t cnt = stat[c], g = 1ull << c, per_launch = std::max<uint64_t>(max_threads / g, 1);
             for (uint64_t x0 = 0; x0 < cnt; x0 += per_launch, ++launches) {
@@ -466,7 +466,7 @@ int sw_batch_fetch(const sw_batch *b, const sw_interval *intervals, uint64_t n, 
 {
     return guarded([&] {
         if (!b || !out || (n && !intervals)) raise(SW_ERR_VALUE, "fetch: a NULL handle or array");
-        sq_require_device(b->device, "the batch");
+        require_device(b->device, "the batch");
         StreamScope scope(SQ_STREAM);
         DevRuns runs(*b);
         DevArray<sw_interval> d_iv(n);
@@ -482,7 +482,7 @@ int sw_markers_fetch(const sw_markers *m, const sw_batch *b, int rows, const uin
 {
     return guarded([&] {
         if (!m || !b || !out) raise(SW_ERR_VALUE, "fetch: a NULL handle");
-        sq_require_device(b->device, "the batch");
+        require_device(b->device, "the batch");
         StreamScope scope(SQ_STREAM);
         MarkerLists L;
         marker_lists(*m, *b, rows, false, select, n_select, L);
@@ -507,7 +507,7 @@ int sw_seqs_export(const sw_seqs *s, uint64_t *offsets, char *blob, uint8_t *fla
 {
     return guarded([&] {
         if (!s) raise(SW_ERR_VALUE, "fetch: a NULL handle");
-        sq_require_device(s->device, "the sequences");
+        require_device(s->device, "the sequences");
         if (offsets) SW_HIP(hipMemcpy(offsets, s->off.p, (s->n + 1) * 8, hipMemcpyDeviceToHost));
         if (blob && s->bytes) SW_HIP(hipMemcpy(blob, s->blob.p, s->bytes, hipMemcpyDeviceToHost));
         if (flags && s->n) SW_HIP(hipMemcpy(flags, s->flags.p, s->n, hipMemcpyDeviceToHost));
@@ -533,7 +533,7 @@ int sw_batch_edit_distances(const sw_batch *b, const sw_interval *r, const sw_in
 {
     return guarded([&] {
         if (!b || (n && (!r || !s || !dist || !strand))) raise(SW_ERR_VALUE, "edit distances: a NULL handle or array");
-        sq_require_device(b->device, "the batch");
+        require_device(b->device, "the batch");
         StreamScope scope(SQ_STREAM);
         DevRuns runs(*b);
         DevArray<sw_interval> d_R(n), d_S(n);
@@ -553,7 +553,7 @@ int sw_markers_row_distances(const sw_markers *m, const sw_batch *b, const uint6
 {
     return guarded([&] {
         if (!m || !b) raise(SW_ERR_VALUE, "edit distances: a NULL handle");
-        sq_require_device(b->device, "the batch");
+        require_device(b->device, "the batch");
         StreamScope scope(SQ_STREAM);
         MarkerLists L;
         marker_lists(*m, *b, 1, true, select, n_select, L);

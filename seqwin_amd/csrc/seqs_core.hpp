@@ -13,39 +13,19 @@ namespace sw {
 namespace {
 
 constexpr uint32_t SQ_TPB = 256, SQ_WAVE = 64, SQ_WPB = SQ_TPB / SQ_WAVE;
-constexpr uint32_t SQ_MAX_BLOCKS = 1u << 22;   // workgroups per launch: 2^30 threads, below the 2^32 a launch may hold
 constexpr uint64_t SQ_MAX_LIST = 0xFFFFFF00ull; // most entries of a list: a thread per entry in workgroups of 256 stays below 2^32 threads
 constexpr uint32_t SQ_PER_WAVE = 16;           // intervals a wave of k_fetch takes at most in one launch (grid stride)
 constexpr uint32_t ED_CAP = 64;                // pattern blocks of the register route: the lanes of a wave (4096 bases)
 constexpr uint32_t ED_CLASSES = 8;             // group widths 1, 2, ... 64, then the striped route
 constexpr uint32_t ED_STRIPE_GROUPS = 1024;    // groups of a launch of the striped route (each owns one row of the scratch)
 
-uint64_t sq_env_u64(const char *v, uint64_t dflt)
-{
-    if (!v || !*v) return dflt;
-    char *end = nullptr;
-    const unsigned long long x = strtoull(v, &end, 10);
-    return (end && *end == 0) ? (uint64_t)x : dflt;
-}
-
-// workgroups per launch; SEQWIN_AMD_SEQ_MAX_BLOCKS (test library) lowers it so that a small list needs several launches
-uint32_t sq_launch_blocks()
-{
-    return (uint32_t)std::max<uint64_t>(std::min<uint64_t>(sq_env_u64(SW_TEST_GETENV("SEQWIN_AMD_SEQ_MAX_BLOCKS"), SQ_MAX_BLOCKS), SQ_MAX_BLOCKS), 1);
-}
+// workgroups per launch: launch_blocks(SQ_BLOCKS_ENV); the switch (test library) lowers it so that a small list needs several launches
+constexpr const char *SQ_BLOCKS_ENV = "SEQWIN_AMD_SEQ_MAX_BLOCKS";
 
 // pattern blocks up to which a pair stays on the register route; SEQWIN_AMD_DIST_LDS_CAP (test library) lowers it
 uint32_t ed_cap_blocks()
 {
-    return (uint32_t)std::max<uint64_t>(std::min<uint64_t>(sq_env_u64(SW_TEST_GETENV("SEQWIN_AMD_DIST_LDS_CAP"), ED_CAP), ED_CAP), 1);
-}
-
-void sq_require_device(int device, const char *what)
-{
-    int cur = -1;
-    SW_HIP(hipGetDevice(&cur));
-    if (cur != device)
-        raise(SW_ERR_VALUE, "%s lives on device %d but the calling thread's current device is %d (sw_set_device)", what, device, cur);
+    return (uint32_t)std::max<uint64_t>(std::min<uint64_t>(env_u64(SW_TEST_GETENV("SEQWIN_AMD_DIST_LDS_CAP"), ED_CAP), ED_CAP), 1);
 }
 
 struct RunTable {   // the batch as the kernels read it

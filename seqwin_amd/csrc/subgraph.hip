@@ -521,22 +521,6 @@ unsigned bit_width(uint64_t x)
     return b;
 }
 
-void require_device_of(int device, const char *what)
-{
-    int cur = -1;
-    SW_HIP(hipGetDevice(&cur));
-    if (cur != device)
-        raise(SW_ERR_VALUE, "%s lives on device %d but the calling thread's current device is %d (sw_set_device)", what, device, cur);
-}
-
-uint64_t env_u64(const char *v, uint64_t dflt)
-{
-    if (!v || !*v) return dflt;
-    char *end = nullptr;
-    const unsigned long long x = strtoull(v, &end, 10);
-    return (end && *end == 0) ? (uint64_t)x : dflt;
-}
-
 // Symmetric CSR of a filtered index, and its seeds in rank order.
 struct Csr {
     uint64_t n = 0, m = 0;
@@ -768,7 +752,7 @@ int sw_index_from_arrays(const sw_node *nodes, uint64_t n_nodes, const sw_edge *
 int sw_index_subgraph_seeds(const sw_index *f, double penalty_th, uint64_t *n_seeds)
 {
     return guarded([&] {
-        require_device_of(f->device, "the index");
+        require_device(f->device, "the index");
         Csr g;
         g.build(*f, 0);
         DevArray<uint32_t> s;
@@ -780,7 +764,7 @@ int sw_index_subgraphs(const sw_index *f, double penalty_th, uint64_t min_nodes,
                        uint64_t n_seeds, sw_subgraphs **out)
 {
     return guarded([&] {
-        require_device_of(f->device, "the index");
+        require_device(f->device, "the index");
         if (n_seeds && !seed_perm) raise(SW_ERR_VALUE, "seed_perm is NULL");
         std::unique_ptr<sw_subgraphs> o(new sw_subgraphs);
         run_subgraphs(*f, penalty_th, min_nodes, max_nodes, seed_perm, n_seeds, *o);
@@ -802,7 +786,7 @@ int sw_subgraphs_export(const sw_subgraphs *sg, uint64_t *offsets, uint64_t *has
                         uint8_t *used_mask, uint64_t *used_hashes)
 {
     return guarded([&] {
-        require_device_of(sg->device, "the subgraphs");
+        require_device(sg->device, "the subgraphs");
         struct { void *dst; const void *src; uint64_t bytes; } c[6] = {
             {offsets, sg->offsets.p, (sg->n_sg + 1) * 8}, {hashes, sg->hashes.p, sg->n_out * 8},
             {edge_offsets, sg->ie_offsets.p, (sg->n_sg + 1) * 8}, {edges, sg->ie_edges.p, sg->n_ie * sizeof(sw_edge)},
@@ -829,7 +813,7 @@ int sw_index_filter_kmers_sg(const sw_index *ix, const sw_index *nodes_from, con
 {
     return guarded([&] {
         const sw_index *nf = nodes_from ? nodes_from : ix;
-        require_device_of(ix->device, "the index");
+        require_device(ix->device, "the index");
         if (nf->device != ix->device || sg->device != ix->device)
             raise(SW_ERR_VALUE, "the index, nodes_from and the subgraphs live on different devices (%d, %d, %d)", ix->device, nf->device, sg->device);
         std::unique_ptr<sw_index> o(new sw_index);

@@ -68,10 +68,10 @@ def _check(batch, queries, assemblies, k, want=None):
         h.close()
 
 
-def _run(tmp_path, queries, asms, k):
+def _run(tmp_path, queries, asms, k, want=None):
     b = _batch(tmp_path, asms)
     try:
-        return _check(b, queries, asms, k)
+        return _check(b, queries, asms, k, want)
     finally:
         b.close()
 
@@ -175,6 +175,68 @@ def test_zero_queries_and_queries_without_seeds(tmp_path):
                 b.best_hits([b"ACGT"], k)
     finally:
         b.close()
+
+
+# ---- run and lane bounds -------------------------------------------------------------------------------------------------------------
+
+TILE = 1024   # k-mers per wave of the batch walk (csrc/kmer_walk.hpp)
+
+
+def _bounds_case(k):
+    """(queries, assemblies, restatement's result, what was added to every query).  Assembly 0, record 0: valid runs of k - 1, k,
+    k + 15, k + 16, 1024 + k - 2, 1024 + k - 1 and 1024 + k bases between single Ns (0, 1, 16, 17, 1023, 1024 and 1025 k-mers: a
+    lane's share and a tile's, one below and one above).  Record 1: sixteen runs, run j starting j places behind a multiple of 16
+    in the record, so that a run starts at each of the 16 places of a packed word.  Assembly 1: the long run without its first base,
+    every k-mer one lane place on.  Queries of k bases: the long run's first k-mer, the last of its first tile, its last (the first of
+    its second tile), and the first k-mer of each of the sixteen runs.  A query without a seed (k = 5: short words repeat in the query
+    text) grows by a base of its run until the restatement finds one."""
+    rng = random.Random(2000 + k)
+    runs = [_rand(rng, n) for n in (k - 1, k, k + 15, k + 16, TILE + k - 2, TILE + k - 1, TILE + k)]
+    long_run = runs[-1]
+    aligned, rec1 = [], bytearray()
+    for j in range(16):
+        rec1 += b"N" if j else b""
+        rec1 += b"N" * ((j - len(rec1)) % 16)
+        aligned.append((len(rec1), _rand(rng, k + 20 + j)))
+        rec1 += aligned[-1][1]
+    assert sorted(p % 16 for p, _ in aligned) == list(range(16))
+    asms = [[b"N".join(runs), bytes(rec1)], [long_run[1:]]]
+    # [run, first base, bases]; the long run's last k-mer grows towards the front, the others towards the back
+    spec = [[long_run, 0, k], [long_run, TILE - 1, k], [long_run, TILE, k]] + [[run, 0, k] for _, run in aligned]
+    while True:
+        queries = [run[s:s + n] for run, s, n in spec]
+        want = H.best_hits(queries, asms, k)
+        short = np.flatnonzero(want["n_seeds"] == 0)
+        if not len(short):
+            break
+        for q in short:
+            run, s, n = spec[q]
+            assert n < len(run) - 1, "the run is used up"
+            spec[q][1] = s - 1 if q == 2 else s
+            spec[q][2] = n + 1
+    return queries, asms, want, [n - k for _, _, n in spec], aligned
+
+
+@pytest.mark.parametrize("k", [21, 5, 32])
+def test_run_and_lane_bounds(tmp_path, k):
+    """tests/test_gpu_screen.py::test_run_and_lane_bounds for the best hits, which walk the batch with the same code: hits at a
+    run's first k-mer, at the last of its first tile, at its last -- the only one of its second tile --, and at the first k-mer
+    of runs that start at each of the 16 places of a packed word (_bounds_case).  On the host, when the case was made: every query
+    has a seed at every k; at k = 21 and 32 every (query, assembly) has one run of the best score; at k = 5 a word of five bases
+    lies in an assembly several times, twelve cells have 2 to 11 runs of the best score and the smallest key wins, as specified."""
+    queries, asms, want, grown, aligned = _bounds_case(k)
+    assert (want["n_seeds"] > 0).all() and (want["seeds"][:, 0] > 0).all()   # no query passes on an empty seed set
+    got, st = _run(tmp_path, queries, asms, k, want)
+    assert st["hits"] >= len(queries)
+    if k >= 15:   # (random k-mers of this length do not repeat: every query is one seed, found where it was cut)
+        long_at = len(asms[0][0]) - (TILE + k)
+        assert not any(grown) and got["n_seeds"].tolist() == [1] * len(queries)
+        assert got["seeds"][:, 0].tolist() == [1] * len(queries) and not got["dist"][:, 0].any() and not got["strand"][:, 0].any()
+        assert got["record"][:, 0].tolist() == [0] * 3 + [1] * 16
+        assert got["end"][:, 0].tolist() == [long_at + k, long_at + TILE - 1 + k, long_at + TILE + k] + [p + k for p, _ in aligned]
+        # assembly 1 holds the long run from its second base on: not its first k-mer, the others one place earlier
+        assert got["seeds"][:, 1].tolist() == [0, 1, 1] + [0] * 16 and got["end"][1:3, 1].tolist() == [TILE - 2 + k, TILE - 1 + k]
+        assert got["record"][1:3, 1].tolist() == [2, 2]
 
 
 # ---- the hooks ---------------------------------------------------------------------------------------------------------------------
