@@ -520,6 +520,38 @@ int sw_hits_stats(const sw_hits *h, uint64_t *counters, double *ms);
 int sw_hits_chunk_hits(const sw_hits *h, uint64_t *hits);
 void sw_hits_free(sw_hits *h);
 
+/* ---- the alignment behind a best hit: start, nident, mismatch, gaps, edit script (csrc/align.hip) ---------------------------------
+ * The canonical optimal alignment of Layer A's pair, by DESIGN.md section 3.2f (tests/tools/align_host.py restates it).  Still NOT
+ * BLAST: no scores, no e-values, no local alignment, none of MarkerMetrics.  With D the infix matrix of Layer A and (m, j*) the cell
+ * that gave dist and end, the traceback repeats, first match wins, until i = 0: (1) j > 0 and P[i-1] = T[j-1], both valid: `=`, to
+ * (i-1, j-1); (2) j > 0 and D[i-1][j-1] + 1 = D[i][j]: `X`, to (i-1, j-1); (3) D[i-1][j] + 1 = D[i][j]: `I`, a pattern base faces a
+ * gap, to (i-1, j); (4) otherwise `D`, a text base faces a gap, to (i, j-1).  a_start = start + j at the stop, nident = #`=`,
+ * mismatch = #`X`, gaps = #`I` + #`D`: nident + mismatch + #I = |P|, nident + mismatch + #D = end - a_start, mismatch + gaps =
+ * dist.  An empty query gives a_start = end = start and no ops, an empty text a_start = start and |P| ops `I`. */
+typedef struct sw_ops sw_ops; /* opaque: the edit scripts of one sw_batch_infix_alignments call, CSR, on the device */
+/* sw_batch_infix_distances plus the traceback of every pair: the same arguments, checks and errors; a_start, nident, mismatch and
+ * gaps are host arrays of n like dist and end.  ops != NULL: *ops receives the scripts -- pair i's ops in pattern order from a_start
+ * to end, one byte each (0 `=`, 1 `X`, 2 `I`, 3 `D`), |P| + #D of them.  counters[8] (may be NULL) = { pairs traced, rounds through
+ * the scratch, pairs on the striped route, pairs with a scratch of their own, scratch bytes at peak, ops written, largest scratch of
+ * one pair in bytes, launches of the store kernels }; ms[3] (may be NULL) = { distances, store pass, walk } (HIP events). */
+int sw_batch_infix_alignments(const sw_batch *b, const uint64_t *offsets, const char *blob, uint64_t n_queries, const sw_infix_pair *pairs,
+                              uint64_t n, uint32_t *dist, uint32_t *end, uint32_t *a_start, uint32_t *nident, uint32_t *mismatch, uint32_t *gaps,
+                              sw_ops **ops, uint64_t *counters, double *ms);
+/* Pairs and bytes of all their scripts (either may be NULL). */
+int sw_ops_sizes(const sw_ops *o, uint64_t *n, uint64_t *bytes);
+/* D2H copies (either may be NULL): offsets[n + 1] into ops[bytes]. */
+int sw_ops_export(const sw_ops *o, uint64_t *offsets, uint8_t *ops);
+void sw_ops_free(sw_ops *o);
+/* sw_batch_best_hits plus the traceback of every winner, run once per chunk of assemblies right behind the chunk's distances.  The
+ * five fields of sw_hits_block are what sw_batch_best_hits gives. */
+int sw_batch_best_hits_aligned(const sw_batch *batch, const uint64_t *offsets, const char *blob, uint64_t n_queries, uint64_t k, sw_hits **out);
+/* sw_hits_block for the fields 0 a_start, 1 nident, 2 mismatch, 3 gaps; a pair without a hit reads 0xFFFFFFFF in all four.  Hits made
+ * by sw_batch_best_hits hold none of them: SW_ERR_VALUE. */
+int sw_hits_align_block(const sw_hits *h, uint64_t field, uint64_t r0, uint64_t r1, uint64_t c0, uint64_t c1, uint32_t *out);
+/* counters[8] as for sw_batch_infix_alignments, summed over the chunks (the two peaks: the largest); ms[2] = { store pass, walk }.
+ * SW_ERR_VALUE for hits made without the alignment. */
+int sw_hits_align_stats(const sw_hits *h, uint64_t *counters, double *ms);
+
 /* ---- multi-GPU merge (one process per GPU; the exchange itself is done by the host side with
  *      torch.distributed / RCCL on the device buffers below).  Together these replace
  *      merge_thread_graphs (cpp/src/seqwin/build_internals.cpp:295-392) across GPUs. -------------- */

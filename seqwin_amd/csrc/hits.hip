@@ -20,13 +20,11 @@
 //   the winner of a (query, assembly) by atomicMax of (score, ~run index): the smallest key wins a tie), k_hit_finish (the winner's
 //   fields, its window as a pair of Layer A), and Layer A on the chunk's pairs.  A chunk whose hits overflow the buffer is redone in
 //   two halves; one assembly that overflows it has the buffer doubled.
-#include "screen_core.hpp"
-#include "seqs_core.hpp"
+#include "hits_core.hpp"
 
 namespace sw {
 namespace {
 
-constexpr hipStream_t HIT_STREAM = SQ_STREAM;
 constexpr uint32_t HIT_BAND_SHIFT = 6;                 // W = 64: part of the specification
 constexpr uint64_t HIT_BUFFER_BYTES = 1ull << 30;      // hit keys and the sort's second buffer together: speed only, no measurement behind it
 constexpr uint64_t HIT_MAX_KEYS = 1ull << 31;          // a run index and a score are 32-bit values
@@ -68,11 +66,7 @@ __global__ __launch_bounds__(SCR_TPB) void k_ix_pack(uint64_t base, uint64_t end
     valid[grp] = v;
 }
 
-struct QueryPack {
-    DevArray<uint32_t> codes[2], valid[2];
-    DevArray<uint64_t> off;   // [nq + 1]
-    uint64_t nq = 0;
-};
+}  // namespace
 
 void pack_queries(const uint8_t *d_text, const uint64_t *offsets, uint64_t nq, QueryPack &P)
 {
@@ -91,16 +85,7 @@ void pack_queries(const uint8_t *d_text, const uint64_t *offsets, uint64_t nq, Q
                   P.valid[1].p);
 }
 
-// bit i set: base g + i of the stream is valid, i < cnt <= 32 (the plane has a word behind its last)
-__device__ __forceinline__ uint32_t plane32(const uint32_t *__restrict__ valid, uint64_t g, uint32_t cnt)
-{
-    const uint64_t w = g >> 5;
-    const uint32_t sh = (uint32_t)(g & 31);
-    uint64_t x = valid[w];
-    if (sh + cnt > 32) x |= (uint64_t)valid[w + 1] << 32;
-    x >>= sh;
-    return (uint32_t)x & (cnt >= 32 ? 0xFFFFFFFFu : (1u << cnt) - 1);
-}
+namespace {
 
 // ---- Layer A: the kernels -------------------------------------------------------------------------------------------------------
 struct IxArgs {
@@ -256,8 +241,10 @@ __global__ __launch_bounds__(SQ_TPB) void k_ix_classify(const sw_infix_pair *__r
     if (cls == IX_CLASSES - 1) atomicMax(stat + 10, (unsigned long long)tn);
 }
 
+}  // namespace
+
 // dist / end of n valid pairs (device list).  counters[6] = { pairs, cells, striped pairs, longest query, launches, block bound }
-void infix_device(const RunTable &t, const QueryPack &P, const sw_infix_pair *d_pairs, const uint32_t *d_out_idx, uint64_t n, uint32_t *d_dist, uint32_t *d_end,
+void infix_device(const Runs &runs, const QueryPack &P, const sw_infix_pair *d_pairs, const uint32_t *d_out_idx, uint64_t n, uint32_t *d_dist, uint32_t *d_end,
                   uint64_t *counters, double *ms_out)
 {
     Event e0, e1;
@@ -276,7 +263,7 @@ void infix_device(const RunTable &t, const QueryPack &P, const sw_infix_pair *d_
         SW_HIP(hipMemcpyAsync(stat, d_stat.p, sizeof stat, hipMemcpyDeviceToHost, HIT_STREAM));
         SW_HIP(hipStreamSynchronize(HIT_STREAM));
         IxArgs a{};
-        a.t = t;
+        a.t = table_of(runs);
         for (int s = 0; s < 2; ++s) {
             a.codes[s] = P.codes[s].p;
             a.valid[s] = P.valid[s].p;
@@ -328,6 +315,8 @@ void infix_device(const RunTable &t, const QueryPack &P, const sw_infix_pair *d_
         ms_out[0] = ms;
     }
 }
+
+namespace {
 
 // ---- Layer B: seeds -------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(SCR_TPB) void k_hit_mult(uint64_t base, uint64_t end, const uint32_t *__restrict__ sidx, const uint32_t *__restrict__ number,
@@ -480,20 +469,11 @@ __global__ __launch_bounds__(SCR_TPB) void k_hit_finish(uint64_t base, uint64_t 
 }  // namespace
 }  // namespace sw
 
-struct sw_hits {
-    int device = 0;
-    uint64_t nq = 0, n_asm = 0, k = 0, n_seeds_total = 0;
-    std::vector<uint32_t> n_seeds;                 // [nq]
-    sw::DevArray<uint32_t> field[5];               // [nq][n_asm] seeds, record, strand, end, dist
-    uint64_t counters[10] = {};
-    double ms[4] = {};
-    std::vector<uint64_t> chunk_hits;
-};
-
 namespace sw {
 namespace {
 
-void batch_best_hits(const sw_batch &b, const uint64_t *offsets, const char *blob, uint64_t nq, uint32_t k, sw_hits &o)
+// align: the traceback of every chunk's winners (align.hip) right behind their distances, while the chunk's windows exist
+void batch_best_hits(const sw_batch &b, const uint64_t *offsets, const char *blob, uint64_t nq, uint32_t k, bool align, sw_hits &o)
 {
     const hipStream_t stream = HIT_STREAM;
     const HostBatch &h = b.host;
@@ -507,6 +487,12 @@ void batch_best_hits(const sw_batch &b, const uint64_t *offsets, const char *blo
         o.field[f].alloc(n_cells);
         if (n_cells) SW_HIP(hipMemsetAsync(o.field[f].p, (f == 0 || f == 2) ? 0 : 0xFF, n_cells * 4, stream));
     }
+    o.aligned = align;
+    if (align)
+        for (int f = 0; f < 4; ++f) {
+            o.afield[f].alloc(n_cells);
+            if (n_cells) SW_HIP(hipMemsetAsync(o.afield[f].p, 0xFF, n_cells * 4, stream));
+        }
     // the key's fields: query | record | orientation | band, the band field one value wider than the largest band (b + 1 is looked at)
     uint64_t max_q = 0, max_rec = 0;
     for (uint64_t q = 0; q < nq; ++q) max_q = std::max(max_q, offsets[q + 1] - offsets[q]);
@@ -653,10 +639,14 @@ void batch_best_hits(const sw_batch &b, const uint64_t *offsets, const char *blo
                 // Layer A on the chunk's winners
                 uint64_t cn[6] = {};
                 double dms[1] = {};
-                infix_device(runs.t, P, pairs.p, out_idx.p, n_pairs, o.field[4].p, o.field[3].p, cn, dms);
+                infix_device(runs_of(runs.t), P, pairs.p, out_idx.p, n_pairs, o.field[4].p, o.field[3].p, cn, dms);
                 aligned += cn[0];
                 striped += cn[2];
                 o.ms[3] += dms[0];
+                if (align) {
+                    uint32_t *const out[4] = {o.afield[0].p, o.afield[1].p, o.afield[2].p, o.afield[3].p};
+                    align_device(runs_of(runs.t), P, pairs.p, out_idx.p, n_pairs, o.field[4].p, o.field[3].p, out, nullptr, nullptr, o.align);
+                }
             }
             a0 = a1;
         }
@@ -664,6 +654,44 @@ void batch_best_hits(const sw_batch &b, const uint64_t *offsets, const char *blo
     SW_HIP(hipStreamSynchronize(stream));
     const uint64_t cn[10] = {hits, n_seeds_total, chunks, splits, launches, aligned, striped, Q.n_distinct, cap_keys, grows};
     memcpy(o.counters, cn, sizeof cn);
+}
+
+}  // namespace
+
+// the checks of a Layer A call, in its order: what a pair says by itself before a handle or a device is touched (arrays_ok: the
+// caller's output arrays are there)
+void check_infix_pairs(const char *what, const sw_batch *b, const uint64_t *offsets, const char *blob, uint64_t n_queries, const sw_infix_pair *pairs, uint64_t n,
+                       bool arrays_ok)
+{
+    check_queries(what, offsets, blob, n_queries);
+    if (n && !pairs) raise(SW_ERR_VALUE, "%s: a NULL handle or array", what);
+    for (uint64_t i = 0; i < n; ++i)
+        if (pairs[i].query >= n_queries || pairs[i].strand > 1 || pairs[i].start > pairs[i].stop)
+            raise(SW_ERR_VALUE, "%s: pair %llu (query %u, strand %u, record %u, [%u, %u)) names no query, no strand or no interval", what,
+                  (unsigned long long)i, pairs[i].query, pairs[i].strand, pairs[i].record, pairs[i].start, pairs[i].stop);
+    if (!b || (n && !arrays_ok)) raise(SW_ERR_VALUE, "%s: a NULL handle or array", what);
+    const std::vector<uint32_t> &rec_len = b->host.rec_len;
+    for (uint64_t i = 0; i < n; ++i)
+        if (pairs[i].record >= rec_len.size() || pairs[i].stop > rec_len[pairs[i].record])
+            raise(SW_ERR_VALUE, "%s: pair %llu (record %u, [%u, %u)) does not lie inside one of the batch's %llu records", what, (unsigned long long)i,
+                  pairs[i].record, pairs[i].start, pairs[i].stop, (unsigned long long)rec_len.size());
+    require_device(b->device, "the batch");
+}
+
+namespace {
+
+void best_hits_entry(const sw_batch *batch, const uint64_t *offsets, const char *blob, uint64_t n_queries, uint64_t k, bool align, sw_hits **out)
+{
+    if (k < 1 || k > 32) raise(SW_ERR_VALUE, "best hits: k-mer length must lie in 1..32 (got %llu)", (unsigned long long)k);
+    if (!batch || !out) raise(SW_ERR_VALUE, "best hits: a NULL handle or array");
+    check_queries("best hits", offsets, blob, n_queries);
+    if (batch->host.rec_len.size() && !batch->d_packed.p) raise(SW_ERR_VALUE, "best hits: the batch holds no packed bases (it must be resident)");
+    require_device(batch->device, "the batch");
+    StreamScope scope(HIT_STREAM);
+    std::unique_ptr<sw_hits> o(new sw_hits);
+    o->device = batch->device;
+    batch_best_hits(*batch, offsets, blob, n_queries, (uint32_t)k, align, *o);
+    *out = o.release();
 }
 
 }  // namespace
@@ -677,19 +705,7 @@ int sw_batch_infix_distances(const sw_batch *b, const uint64_t *offsets, const c
                              uint32_t *dist, uint32_t *end, uint64_t *counters, double *ms)
 {
     return guarded([&] {
-        check_queries("infix distances", offsets, blob, n_queries);
-        if (n && !pairs) raise(SW_ERR_VALUE, "infix distances: a NULL handle or array");
-        for (uint64_t i = 0; i < n; ++i)   // what a pair says by itself, before a handle or a device is touched
-            if (pairs[i].query >= n_queries || pairs[i].strand > 1 || pairs[i].start > pairs[i].stop)
-                raise(SW_ERR_VALUE, "infix distances: pair %llu (query %u, strand %u, record %u, [%u, %u)) names no query, no strand or no interval",
-                      (unsigned long long)i, pairs[i].query, pairs[i].strand, pairs[i].record, pairs[i].start, pairs[i].stop);
-        if (!b || (n && (!dist || !end))) raise(SW_ERR_VALUE, "infix distances: a NULL handle or array");
-        const std::vector<uint32_t> &rec_len = b->host.rec_len;
-        for (uint64_t i = 0; i < n; ++i)
-            if (pairs[i].record >= rec_len.size() || pairs[i].stop > rec_len[pairs[i].record])
-                raise(SW_ERR_VALUE, "infix distances: pair %llu (record %u, [%u, %u)) does not lie inside one of the batch's %llu records", (unsigned long long)i,
-                      pairs[i].record, pairs[i].start, pairs[i].stop, (unsigned long long)rec_len.size());
-        require_device(b->device, "the batch");
+        check_infix_pairs("infix distances", b, offsets, blob, n_queries, pairs, n, dist && end);
         StreamScope scope(HIT_STREAM);
         DevRuns runs(*b);
         const uint64_t total = n_queries ? offsets[n_queries] : 0;
@@ -700,7 +716,7 @@ int sw_batch_infix_distances(const sw_batch *b, const uint64_t *offsets, const c
         DevArray<sw_infix_pair> d_pairs(n);
         DevArray<uint32_t> d_dist(n), d_end(n);
         if (n) SW_HIP(hipMemcpyAsync(d_pairs.p, pairs, n * sizeof(sw_infix_pair), hipMemcpyHostToDevice, HIT_STREAM));
-        infix_device(runs.t, P, d_pairs.p, nullptr, n, d_dist.p, d_end.p, counters, ms);
+        infix_device(runs_of(runs.t), P, d_pairs.p, nullptr, n, d_dist.p, d_end.p, counters, ms);
         if (n) {
             SW_HIP(hipMemcpy(dist, d_dist.p, n * 4, hipMemcpyDeviceToHost));
             SW_HIP(hipMemcpy(end, d_end.p, n * 4, hipMemcpyDeviceToHost));
@@ -710,18 +726,12 @@ int sw_batch_infix_distances(const sw_batch *b, const uint64_t *offsets, const c
 
 int sw_batch_best_hits(const sw_batch *batch, const uint64_t *offsets, const char *blob, uint64_t n_queries, uint64_t k, sw_hits **out)
 {
-    return guarded([&] {
-        if (k < 1 || k > 32) raise(SW_ERR_VALUE, "best hits: k-mer length must lie in 1..32 (got %llu)", (unsigned long long)k);
-        if (!batch || !out) raise(SW_ERR_VALUE, "best hits: a NULL handle or array");
-        check_queries("best hits", offsets, blob, n_queries);
-        if (batch->host.rec_len.size() && !batch->d_packed.p) raise(SW_ERR_VALUE, "best hits: the batch holds no packed bases (it must be resident)");
-        require_device(batch->device, "the batch");
-        StreamScope scope(HIT_STREAM);
-        std::unique_ptr<sw_hits> o(new sw_hits);
-        o->device = batch->device;
-        batch_best_hits(*batch, offsets, blob, n_queries, (uint32_t)k, *o);
-        *out = o.release();
-    });
+    return guarded([&] { best_hits_entry(batch, offsets, blob, n_queries, k, false, out); });
+}
+
+int sw_batch_best_hits_aligned(const sw_batch *batch, const uint64_t *offsets, const char *blob, uint64_t n_queries, uint64_t k, sw_hits **out)
+{
+    return guarded([&] { best_hits_entry(batch, offsets, blob, n_queries, k, true, out); });
 }
 
 int sw_hits_sizes(const sw_hits *h, uint64_t *n_queries, uint64_t *n_assemblies, uint64_t *n_seeds, uint64_t *k)

@@ -1,0 +1,81 @@
+// hits_core.hpp -- what hits.hip (seed vote + infix distance) and align.hip (the traceback behind that distance) share: the packed
+// queries, the result object, and the host entry points each file offers the other.  Host functions link across the two files;
+// device functions do not, so the one both need (plane32) lives here.
+#pragma once
+#include <vector>
+
+#include "screen_core.hpp"
+#include "seqs_core.hpp"
+
+namespace sw {
+
+// Strand s of the query text: base x of query q lies at index off[q] + x of stream s; stream 1 holds the reverse complements.
+// codes: 16 bases per word as the batch packs them; valid: a bit per base.
+struct QueryPack {
+    DevArray<uint32_t> codes[2], valid[2];
+    DevArray<uint64_t> off;   // [nq + 1]
+    uint64_t nq = 0;
+};
+
+// counters[8] = { pairs traced, rounds, pairs on the striped route, pairs with a scratch of their own, scratch bytes at peak, ops
+// written, largest scratch of one pair in bytes, launches of the store kernels }; ms[2] = { store pass, walk }
+struct AlignStats {
+    uint64_t counters[8] = {};
+    double ms[2] = {};
+};
+
+// RunTable (seqs_core.hpp) has internal linkage like every type of that header; this is the same table as the two files hand it to
+// each other (runs_of / table_of below)
+struct Runs {
+    const uint32_t *packed;
+    const uint64_t *rec_base;
+    const uint32_t *rec_len, *rec_run_off, *run_pos, *run_len;
+    uint64_t n_records;
+};
+
+// hits.hip
+void pack_queries(const uint8_t *d_text, const uint64_t *offsets, uint64_t nq, QueryPack &P);
+void infix_device(const Runs &t, const QueryPack &P, const sw_infix_pair *d_pairs, const uint32_t *d_out_idx, uint64_t n, uint32_t *d_dist, uint32_t *d_end,
+                  uint64_t *counters, double *ms_out);
+void check_infix_pairs(const char *what, const sw_batch *b, const uint64_t *offsets, const char *blob, uint64_t n_queries, const sw_infix_pair *pairs, uint64_t n,
+                       bool arrays_ok);
+
+// align.hip: the canonical traceback of n valid pairs (device list) whose Layer A results lie at d_dist / d_end [out index of the
+// pair].  out[4] = a_start, nident, mismatch, gaps at the same index.  d_ops != nullptr: pair i's script is written so that it ends
+// at d_ops[d_ops_end[i]] (exclusive), the slot in front of it holding |query| + dist bytes.  st is added to.
+void align_device(const Runs &t, const QueryPack &P, const sw_infix_pair *d_pairs, const uint32_t *d_out_idx, uint64_t n, const uint32_t *d_dist,
+                  const uint32_t *d_end, uint32_t *const out[4], uint8_t *d_ops, const uint64_t *d_ops_end, AlignStats &st);
+
+namespace {
+
+constexpr hipStream_t HIT_STREAM = SQ_STREAM;
+
+inline Runs runs_of(const RunTable &t) { return Runs{t.packed, t.rec_base, t.rec_len, t.rec_run_off, t.run_pos, t.run_len, t.n_records}; }
+inline RunTable table_of(const Runs &r) { return RunTable{r.packed, r.rec_base, r.rec_len, r.rec_run_off, r.run_pos, r.run_len, r.n_records}; }
+
+// bit i set: base g + i of the stream is valid, i < cnt <= 32 (the plane has a word behind its last)
+__device__ __forceinline__ uint32_t plane32(const uint32_t *__restrict__ valid, uint64_t g, uint32_t cnt)
+{
+    const uint64_t w = g >> 5;
+    const uint32_t sh = (uint32_t)(g & 31);
+    uint64_t x = valid[w];
+    if (sh + cnt > 32) x |= (uint64_t)valid[w + 1] << 32;
+    x >>= sh;
+    return (uint32_t)x & (cnt >= 32 ? 0xFFFFFFFFu : (1u << cnt) - 1);
+}
+
+}  // namespace
+}  // namespace sw
+
+struct sw_hits {
+    int device = 0;
+    uint64_t nq = 0, n_asm = 0, k = 0, n_seeds_total = 0;
+    std::vector<uint32_t> n_seeds;                 // [nq]
+    sw::DevArray<uint32_t> field[5];               // [nq][n_asm] seeds, record, strand, end, dist
+    uint64_t counters[10] = {};
+    double ms[4] = {};
+    std::vector<uint64_t> chunk_hits;
+    bool aligned = false;                          // made by sw_batch_best_hits_aligned
+    sw::DevArray<uint32_t> afield[4];              // [nq][n_asm] a_start, nident, mismatch, gaps (aligned only)
+    sw::AlignStats align;
+};

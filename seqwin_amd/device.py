@@ -152,16 +152,51 @@ class Batch:
         d.update(distance_ms=ms[0])
         return dist, end, d
 
-    def best_hits(self, queries, kmerlen: int) -> "BestHits":
+    def infix_alignments(self, queries, pairs, ops: bool = False, stats: bool = False):
+        """:meth:`infix_distances` plus the canonical optimal alignment behind each distance (csrc/align.hip, DESIGN.md section
+        3.2f): ``(dist, end, start, nident, mismatch, gaps)``, all uint32 -- the located copy is ``[start, end)`` of the record,
+        ``nident`` / ``mismatch`` count the ``=`` / ``X`` columns and ``gaps`` both kinds of gap column, so that ``mismatch + gaps ==
+        dist``.  ``ops=True`` adds ``(offsets, ops)``: the edit scripts in CSR form, pair i's ops in pattern order from ``start`` to
+        ``end``, one uint8 each (OP_MATCH 0, OP_MISMATCH 1, OP_INSERT 2 -- a query base faces a gap --, OP_DELETE 3 -- a text base
+        faces a gap); :func:`seqwin_amd.markers.cigar` renders them.  Not BLAST.  ``stats=True`` adds the call's counters last."""
+        offs, blob, nq = _query_csr(queries)
+        pr = _infix_pairs(pairs)
+        out = [np.empty(len(pr), np.uint32) for _ in range(6)]
+        c = (c_u64 * 8)()
+        ms = (ctypes.c_double * 3)()
+        h = c_vp()
+        check(lib.sw_batch_infix_alignments(self._h, _ptr(offs), blob, c_u64(nq), _ptr(pr), c_u64(len(pr)), *[_ptr(a) for a in out],
+                                            ctypes.byref(h) if ops else None, c, ms))
+        res = tuple(out)
+        if ops:
+            try:
+                n, nb = c_u64(), c_u64()
+                check(lib.sw_ops_sizes(h, ctypes.byref(n), ctypes.byref(nb)))
+                o_off = np.empty(n.value + 1, np.uint64)
+                o_ops = np.empty(nb.value, np.uint8)
+                check(lib.sw_ops_export(h, _ptr(o_off), _ptr(o_ops) if nb.value else None))
+            finally:
+                lib.sw_ops_free(h)
+            res += (o_off, o_ops)
+        if stats:
+            d = dict(zip(_ALIGN_COUNTERS, (int(x) for x in c)))
+            d.update(distance_ms=ms[0], store_ms=ms[1], walk_ms=ms[2])
+            res += (d,)
+        return res
+
+    def best_hits(self, queries, kmerlen: int, align: bool = False) -> "BestHits":
         """For every query (a list of ``str`` or ``bytes``) and every assembly: the best seeded locus and the exact infix edit
         distance of the query to the best substring there (csrc/hits.hip).  A seed is a canonical
         ``kmerlen``-mer that exactly one window of ALL the query text has and that is not its own reverse complement: a query whose
         k-mers are shared with another query, or repeat inside it, loses them as seeds -- deliberately, one hit means one diagonal.
-        Not BLAST: no scores, no e-values, no local alignment, one locus per pair.  ValueError for a k-mer length outside 1..32."""
+        Not BLAST: no scores, no e-values, no local alignment, one locus per pair.  ValueError for a k-mer length outside 1..32.
+        ``align=True`` also traces every winner's alignment (:meth:`infix_alignments` on its window): the result then answers
+        ``start()``, ``nident()``, ``mismatch()``, ``gaps()`` and ``intervals()``."""
         offs, blob, nq = _query_csr(queries)
         h = c_vp()
-        check(lib.sw_batch_best_hits(self._h, _ptr(offs), blob, c_u64(nq), c_u64(int(kmerlen)), ctypes.byref(h)))
-        return BestHits(h)
+        fn = lib.sw_batch_best_hits_aligned if align else lib.sw_batch_best_hits
+        check(fn(self._h, _ptr(offs), blob, c_u64(nq), c_u64(int(kmerlen)), ctypes.byref(h)))
+        return BestHits(h, aligned=bool(align))
 
     def fetch(self, intervals, stats: bool = False):
         """The text of ``intervals`` (INTERVAL_DTYPE or an (n, 3) array of record, start, stop; ``record`` is the batch's global
@@ -203,6 +238,8 @@ INTERVAL_DTYPE = np.dtype([("record", "<u4"), ("start", "<u4"), ("stop", "<u4")]
 SEQ_INEXACT = 1
 INFIX_PAIR_DTYPE = np.dtype([("query", "<u4"), ("strand", "<u4"), ("record", "<u4"), ("start", "<u4"), ("stop", "<u4")])
 NO_HIT = 0xFFFFFFFF   # record, end and dist of a (query, assembly) without a hit
+OP_MATCH, OP_MISMATCH, OP_INSERT, OP_DELETE = 0, 1, 2, 3   # the bytes of an edit script: = X I D
+_ALIGN_COUNTERS = ("pairs", "rounds", "striped_pairs", "own_scratch_pairs", "scratch_peak_bytes", "ops", "largest_pair_bytes", "store_launches")
 
 
 def _query_csr(queries):
@@ -601,12 +638,12 @@ class Markers:
         o = offs.astype(np.int64)
         return batch.screen([blob[o[i]:o[i + 1]] for i in range(len(o) - 1)], kmerlen)
 
-    def best_hits(self, batch: "Batch", kmerlen: int, select=None) -> "BestHits":
+    def best_hits(self, batch: "Batch", kmerlen: int, select=None, align: bool = False) -> "BestHits":
         """:meth:`Batch.best_hits` of the representatives' text -- ``sequences(batch, "reps", select)``, in that order -- against
         every assembly of ``batch``.  ``kmerlen`` is the caller's choice; it need not be the graph's k."""
         offs, blob, _ = self.sequences(batch, "reps", select)
         o = offs.astype(np.int64)
-        return batch.best_hits([blob[o[i]:o[i + 1]] for i in range(len(o) - 1)], kmerlen)
+        return batch.best_hits([blob[o[i]:o[i + 1]] for i in range(len(o) - 1)], kmerlen, align=align)
 
     def candidates(self, min_len: int) -> np.ndarray:
         """Indices of the subgraphs the reference keeps (markers.py:514-517): len >= min_len, neither single nor dup."""
@@ -822,10 +859,12 @@ class BestHits:
     which ends at record position ``end``.  A pair without a hit reads seeds 0, strand 0 and NO_HIT elsewhere.  It covers the ground
     of ``eval_markers`` (src/seqwin/markers.py:607-696), has no counterpart in the reference, is not BLAST and fills none of
     ``MarkerMetrics``.  A single-device object on a resident batch.  ``rows`` (queries) / ``cols`` (assemblies) are None (all), a
-    ``(lo, hi)`` pair, a slice or a range."""
+    ``(lo, hi)`` pair, a slice or a range.  Made with ``align=True`` it also holds the canonical alignment of every hit (csrc/align.hip,
+    DESIGN.md section 3.2f): ``start``, ``nident``, ``mismatch`` and ``gaps``, NO_HIT where there is no hit."""
 
-    def __init__(self, handle: c_vp):
+    def __init__(self, handle: c_vp, aligned: bool = False):
         self._h = handle
+        self._aligned = aligned
 
     def sizes(self):
         """(queries, assemblies, seeds of all queries, k)"""
@@ -861,6 +900,51 @@ class BestHits:
 
     def dist(self, rows=None, cols=None) -> np.ndarray:
         return self._block(4, rows, cols)
+
+    def _align_block(self, field: int, rows, cols) -> np.ndarray:
+        if not self._aligned:
+            raise ValueError("these best hits were made without align=True")
+        nq, na, _, _ = self.sizes()
+        (r0, r1), (c0, c1) = _block_range(rows, nq), _block_range(cols, na)
+        out = np.empty((max(r1 - r0, 0), max(c1 - c0, 0)), np.uint32)
+        check(lib.sw_hits_align_block(self._h, c_u64(field), c_u64(r0), c_u64(r1), c_u64(c0), c_u64(c1), _ptr(out)))
+        return out
+
+    def start(self, rows=None, cols=None) -> np.ndarray:
+        """uint32[rows, cols]: where the located copy starts in its record; it is ``[start, end)``."""
+        return self._align_block(0, rows, cols)
+
+    def nident(self, rows=None, cols=None) -> np.ndarray:
+        return self._align_block(1, rows, cols)
+
+    def mismatch(self, rows=None, cols=None) -> np.ndarray:
+        return self._align_block(2, rows, cols)
+
+    def gaps(self, rows=None, cols=None) -> np.ndarray:
+        """uint32[rows, cols]: gap columns of either side; ``mismatch + gaps == dist``."""
+        return self._align_block(3, rows, cols)
+
+    def intervals(self, rows=None, cols=None):
+        """``(intervals, row, col)`` of the block's pairs WITH a hit, row-major: INTERVAL_DTYPE ``(record, start, end)`` as
+        :meth:`Batch.fetch` takes them (the text of a strand-1 hit is the reverse complement of the query's copy), and the query
+        and assembly index of each."""
+        rec, a, e = self.record(rows, cols), self.start(rows, cols), self.end(rows, cols)
+        nq, na, _, _ = self.sizes()
+        r0, c0 = _block_range(rows, nq)[0], _block_range(cols, na)[0]
+        r, c = np.nonzero(rec != np.uint32(NO_HIT))
+        iv = np.empty(len(r), INTERVAL_DTYPE)
+        iv["record"], iv["start"], iv["stop"] = rec[r, c], a[r, c], e[r, c]
+        return iv, r + r0, c + c0
+
+    def align_stats(self) -> dict:
+        if not self._aligned:
+            raise ValueError("these best hits were made without align=True")
+        c = (c_u64 * 8)()
+        ms = (ctypes.c_double * 2)()
+        check(lib.sw_hits_align_stats(self._h, c, ms))
+        d = dict(zip(_ALIGN_COUNTERS, (int(x) for x in c)))
+        d.update(store_ms=ms[0], walk_ms=ms[1])
+        return d
 
     def stats(self) -> dict:
         c = (c_u64 * 10)()

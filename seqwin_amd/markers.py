@@ -242,3 +242,56 @@ def hit_summary(h, lengths, n_tar: int, min_identity: float = 0.9) -> np.ndarray
         out[name] = block.sum(axis=1) / block.shape[1]
         out[f_name] = np.where(np.isnan(ln), np.nan, near[:, cols].sum(axis=1) / block.shape[1])
     return out
+
+
+ALIGNMENT_SUMMARY_DTYPE = np.dtype([("identity_tar", "<f8"), ("f_tar", "<f8"), ("distance_neg", "<f8"), ("f_neg", "<f8")])
+
+
+def alignment_summary(h, lengths, n_tar: int) -> np.ndarray:
+    """Per query of a :class:`BestHits` made with ``align=True``, with ``lengths`` the queries' lengths, the targets the first
+    ``n_tar`` columns and the non-targets the rest: ``identity_tar`` = the sum of ``nident`` over the targets' hits / len / n_tar,
+    ``distance_neg`` = the sum of ``mismatch + gaps`` over the non-targets' hits / len / n_neg -- the formulas of ``_get_avg_ident``
+    and ``_get_avg_dist`` (src/seqwin/markers.py:531-604) applied to the canonical alignment at one seeded locus --, ``f_tar`` /
+    ``f_neg`` = the share of the group's assemblies with a hit, all in float64.  A query of length 0, and an empty group, read
+    ``nan``.  The names are deliberately not those of ``MarkerMetrics``: this is not BLAST's best hit, and nothing of it is written
+    into ``signatures.csv``."""
+    nident = np.asarray(h.nident(), np.uint32)
+    edits = np.asarray(h.mismatch(), np.uint32).astype(np.float64) + np.asarray(h.gaps(), np.uint32).astype(np.float64)
+    lengths = np.asarray(lengths, np.int64).reshape(-1)
+    if nident.ndim != 2 or lengths.shape != (nident.shape[0],) or (lengths < 0).any():
+        raise ValueError(f"hits of shape {nident.shape} against {lengths.shape} query lengths")
+    n_tar = int(n_tar)
+    if not 0 <= n_tar <= nident.shape[1]:
+        raise ValueError(f"n_tar = {n_tar} lies outside the {nident.shape[1]} assemblies")
+    out = np.zeros(len(lengths), ALIGNMENT_SUMMARY_DTYPE)
+    ln = lengths.astype(np.float64)
+    ln[ln == 0] = np.nan
+    hit = nident != np.uint32(0xFFFFFFFF)
+    for name, f_name, cols, val in (("identity_tar", "f_tar", slice(0, n_tar), np.where(hit, nident.astype(np.float64), 0.0)),
+                                    ("distance_neg", "f_neg", slice(n_tar, None), np.where(hit, edits, 0.0))):
+        block = val[:, cols]
+        if block.shape[1] == 0:
+            out[name] = out[f_name] = np.nan
+            continue
+        out[name] = block.sum(axis=1) / ln / block.shape[1]
+        out[f_name] = np.where(np.isnan(ln), np.nan, hit[:, cols].sum(axis=1) / block.shape[1])
+    return out
+
+
+def cigar(offsets, ops) -> list:
+    """The edit scripts of :meth:`Batch.infix_alignments` (``ops=True``) as run-length strings such as ``12=1X3=2I``: ``=`` match,
+    ``X`` mismatch, ``I`` a query base facing a gap, ``D`` a text base facing a gap; an empty script is the empty string."""
+    offsets = np.asarray(offsets, np.uint64).astype(np.int64)
+    ops = np.asarray(ops, np.uint8)
+    if offsets.ndim != 1 or len(offsets) < 1 or offsets[0] != 0 or (np.diff(offsets) < 0).any() or offsets[-1] != len(ops) or (ops > 3).any():
+        raise ValueError("offsets and ops are no edit scripts in CSR form")
+    out = []
+    for a, b in zip(offsets[:-1], offsets[1:]):
+        s = ops[a:b]
+        if not len(s):
+            out.append("")
+            continue
+        heads = np.flatnonzero(np.concatenate(([True], s[1:] != s[:-1])))
+        runs = np.diff(np.concatenate((heads, [len(s)])))
+        out.append("".join(f"{int(n)}{'=XID'[int(s[i])]}" for i, n in zip(heads, runs)))
+    return out
