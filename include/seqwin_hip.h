@@ -552,6 +552,33 @@ int sw_hits_align_block(const sw_hits *h, uint64_t field, uint64_t r0, uint64_t 
  * SW_ERR_VALUE for hits made without the alignment. */
 int sw_hits_align_stats(const sw_hits *h, uint64_t *counters, double *ms);
 
+/* ---- every seeded locus of a (query, assembly) pair: repeat counts and the sum of nident (csrc/hits.hip, loci mode) -----------------
+ * Stands where eval_markers' n_hits / avg_nident columns stand; by DESIGN.md section 3.2g (tests/tools/loci_host.py restates it).
+ * Still NOT BLAST and fills none of MarkerMetrics.  A candidate (r, o, b) of section 3.2e is a locus iff its score reaches min_seeds
+ * and no candidate of the same (query, r, o) within two bands has a larger score, or the same score in a smaller band.  Every locus
+ * gets the window, the distance and the canonical alignment a winner gets.  The list ascends by (query, record, orientation, band);
+ * locus j is a duplicate iff locus j - 1 has the same query, record, strand, a_start and end.  Per (query, assembly): n_loci counts
+ * the loci that are no duplicates, sum_nident adds their nident; 0 where there is none.
+ * sw_batch_best_hits_aligned plus the loci: the fields of sw_hits_block / sw_hits_align_block are what that call gives, whatever
+ * min_seeds is.  min_seeds == 0 (checked before a device is touched, behind k), the largest n_loci times the longest query reaching
+ * 2^32 -> SW_ERR_VALUE. */
+int sw_batch_best_hits_loci(const sw_batch *batch, const uint64_t *offsets, const char *blob, uint64_t n_queries, uint64_t k, uint64_t min_seeds,
+                            sw_hits **out);
+/* Loci of all pairs, and how many of them are duplicates (either may be NULL).  This and the three calls below: SW_ERR_VALUE for hits
+ * made without the loci. */
+int sw_hits_loci_sizes(const sw_hits *h, uint64_t *n_loci_total, uint64_t *n_dup);
+/* D2H copies, a NULL array is skipped: cell_offsets[n_queries * n_assemblies + 1] -- the loci of pair (q, a) are entries
+ * [cell_offsets[q * n_assemblies + a], cell_offsets[q * n_assemblies + a + 1]) --, and the list's columns, n_loci_total entries each
+ * (strand and dup are 0 or 1). */
+int sw_hits_loci(const sw_hits *h, uint64_t *cell_offsets, uint32_t *query, uint32_t *assembly, uint32_t *record, uint32_t *strand, uint32_t *band,
+                 uint32_t *seeds, uint32_t *dist, uint32_t *end, uint32_t *a_start, uint32_t *nident, uint32_t *mismatch, uint32_t *gaps, uint32_t *dup);
+/* sw_hits_block for the fields 0 n_loci, 1 sum_nident. */
+int sw_hits_loci_block(const sw_hits *h, uint64_t field, uint64_t r0, uint64_t r1, uint64_t c0, uint64_t c1, uint32_t *out);
+/* counters[5] = { loci, duplicates, most loci of one pair (duplicates not counted), pairs aligned for the list, rounds of their
+ * traceback through the scratch }; ms[4] = { peaks + compaction, distances, traceback, final ordering + reduction } (HIP events,
+ * the first three summed over the chunks). */
+int sw_hits_loci_stats(const sw_hits *h, uint64_t *counters, double *ms);
+
 /* ---- multi-GPU merge (one process per GPU; the exchange itself is done by the host side with
  *      torch.distributed / RCCL on the device buffers below).  Together these replace
  *      merge_thread_graphs (cpp/src/seqwin/build_internals.cpp:295-392) across GPUs. -------------- */

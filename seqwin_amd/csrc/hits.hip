@@ -20,6 +20,10 @@
 //   the winner of a (query, assembly) by atomicMax of (score, ~run index): the smallest key wins a tie), k_hit_finish (the winner's
 //   fields, its window as a pair of Layer A), and Layer A on the chunk's pairs.  A chunk whose hits overflow the buffer is redone in
 //   two halves; one assembly that overflows it has the buffer doubled.
+// Loci mode (sw_batch_best_hits_loci; tests/tools/loci_host.py restates it): behind a chunk's winners, every
+//   run that is a local maximum of the score over two bands to either side (k_hit_peaks) is listed (k_hit_loci), measured and traced
+//   like a winner; after the last chunk the lists are gathered into (query, record, orientation, band) order (k_loci_bounds, a scan,
+//   k_loci_gather), duplicates are marked (k_hit_dups) and every cell is reduced by one thread (k_loci_reduce).
 #include "hits_core.hpp"
 
 namespace sw {
@@ -466,15 +470,218 @@ __global__ __launch_bounds__(SCR_TPB) void k_hit_finish(uint64_t base, uint64_t 
     out_idx[at] = (uint32_t)cell;
 }
 
+// ---- Layer B: every locus ------------------------------------------------------------------------------
+enum { LF_QUERY, LF_ASM, LF_RECORD, LF_STRAND, LF_BAND, LF_SEEDS, LF_DIST, LF_END, LF_START, LF_NIDENT, LF_MISMATCH, LF_GAPS, LF_DUP };
+constexpr int LF_CHUNK = LF_DUP;   // what a chunk's list holds: everything but dup, which only the final order defines
+
+struct LociPtrs {
+    uint32_t *f[LF_CHUNK];
+};
+
+// the score of run r as k_hit_vote computes it
+__device__ __forceinline__ uint64_t run_score(const uint64_t *__restrict__ ukey, const uint32_t *__restrict__ upos, uint64_t n_runs, uint64_t n_keys, uint64_t r)
+{
+    const uint64_t next = r + 1 < n_runs ? upos[r + 1] : n_keys;
+    uint64_t score = next - upos[r];
+    if (r + 1 < n_runs && ukey[r + 1] == ukey[r] + 1) score += (r + 2 < n_runs ? upos[r + 2] : n_keys) - next;
+    return score;
+}
+
+// run r is a locus: its score reaches min_seeds, and no run of the same (query, record, orientation) within two bands beats it -- a
+// larger score, or the same score in a smaller band.  The keys are distinct and sorted, so such a run lies within two places; the
+// fields are compared, not key +- 2 (the band field is one value wider than the largest band: b + 2 may carry)
+__global__ __launch_bounds__(SCR_TPB) void k_hit_peaks(uint64_t base, uint64_t end, const uint64_t *__restrict__ ukey, const uint32_t *__restrict__ upos, uint64_t n_runs,
+                                                       uint64_t n_keys, uint32_t band_bits, uint64_t min_seeds, uint8_t *__restrict__ flag)
+{
+    const uint64_t r = base + (uint64_t)blockIdx.x * SCR_TPB + threadIdx.x;
+    if (r >= end) return;
+    const uint64_t mask = (1ull << band_bits) - 1, key = ukey[r], grp = key >> band_bits, band = key & mask;
+    const uint64_t s = run_score(ukey, upos, n_runs, n_keys, r);
+    bool locus = s >= min_seeds;
+    for (uint64_t d = 1; d <= 2 && locus; ++d) {
+        if (r >= d) {
+            const uint64_t y = ukey[r - d];
+            if ((y >> band_bits) == grp && band - (y & mask) <= 2 && run_score(ukey, upos, n_runs, n_keys, r - d) >= s) locus = false;
+        }
+        if (r + d < n_runs) {
+            const uint64_t y = ukey[r + d];
+            if ((y >> band_bits) == grp && (y & mask) - band <= 2 && run_score(ukey, upos, n_runs, n_keys, r + d) > s) locus = false;
+        }
+    }
+    flag[r] = locus ? 1 : 0;
+}
+
+// flagged run r is entry at[r] of the chunk's list: its fields, and its window as a pair of Layer A
+__global__ __launch_bounds__(SCR_TPB) void k_hit_loci(uint64_t base, uint64_t end, const uint8_t *__restrict__ flag, const uint32_t *__restrict__ at,
+                                                      const uint64_t *__restrict__ ukey, const uint32_t *__restrict__ upos, uint64_t n_runs, uint64_t n_keys,
+                                                      const uint64_t *__restrict__ qoff, const uint32_t *__restrict__ rec_len, const uint32_t *__restrict__ rec_asm,
+                                                      uint32_t k, uint32_t band_bits, uint32_t rec_bits, LociPtrs out, sw_infix_pair *__restrict__ pairs)
+{
+    const uint64_t r = base + (uint64_t)blockIdx.x * SCR_TPB + threadIdx.x;
+    if (r >= end || !flag[r]) return;
+    const uint32_t j = at[r];
+    const uint64_t key = ukey[r], band = key & ((1ull << band_bits) - 1), q = key >> (band_bits + 1 + rec_bits);
+    const uint32_t o = (uint32_t)(key >> band_bits) & 1u, rec = (uint32_t)((key >> (band_bits + 1)) & ((1ull << rec_bits) - 1));
+    out.f[LF_QUERY][j] = (uint32_t)q;
+    out.f[LF_ASM][j] = rec_asm[rec];
+    out.f[LF_RECORD][j] = rec;
+    out.f[LF_STRAND][j] = o;
+    out.f[LF_BAND][j] = (uint32_t)band;
+    out.f[LF_SEEDS][j] = (uint32_t)run_score(ukey, upos, n_runs, n_keys, r);
+    const long long m = (long long)(qoff[q + 1] - qoff[q]), s0 = (long long)(band << HIT_BAND_SHIFT) - (m - (long long)k);
+    const long long lo = s0 - 64 > 0 ? s0 - 64 : 0, len = rec_len[rec], hi = s0 + 192 + m < len ? s0 + 192 + m : len;
+    pairs[j] = sw_infix_pair{(uint32_t)q, o, rec, (uint32_t)lo, (uint32_t)hi};
+}
+
+// entry j of a chunk's list is entry g0 + j of all chunks' lists, one behind the other.  A cell's entries are contiguous there (an
+// assembly belongs to one chunk): the first one writes first[cell], the last one past[cell]
+__global__ __launch_bounds__(SCR_TPB) void k_loci_bounds(uint64_t base, uint64_t end, const uint32_t *__restrict__ query, const uint32_t *__restrict__ assembly,
+                                                         uint64_t n, uint64_t g0, uint64_t n_asm, uint64_t *__restrict__ first, uint64_t *__restrict__ past)
+{
+    const uint64_t j = base + (uint64_t)blockIdx.x * SCR_TPB + threadIdx.x;
+    if (j >= end) return;
+    const uint64_t cell = query[j] * n_asm + assembly[j];
+    if (j == 0 || query[j - 1] * n_asm + assembly[j - 1] != cell) first[cell] = g0 + j;
+    if (j + 1 == n || query[j + 1] * n_asm + assembly[j + 1] != cell) past[cell] = g0 + j + 1;
+}
+
+struct CellCount {
+    const uint64_t *first, *past;
+    uint64_t n;
+    __host__ __device__ uint64_t operator()(uint64_t c) const { return c < n ? past[c] - first[c] : 0ull; }
+};
+
+// a chunk's entries to their place in the final order: the cell's offset + the entry's rank inside its cell
+__global__ __launch_bounds__(SCR_TPB) void k_loci_gather(uint64_t base, uint64_t end, LociPtrs in, uint64_t g0, uint64_t n_asm, const uint64_t *__restrict__ first,
+                                                         const uint64_t *__restrict__ cell_off, LociPtrs out)
+{
+    const uint64_t j = base + (uint64_t)blockIdx.x * SCR_TPB + threadIdx.x;
+    if (j >= end) return;
+    const uint64_t cell = in.f[LF_QUERY][j] * n_asm + in.f[LF_ASM][j], dst = cell_off[cell] + (g0 + j - first[cell]);
+#pragma unroll
+    for (int f = 0; f < LF_CHUNK; ++f) out.f[f][dst] = in.f[f][j];
+}
+
+// locus j repeats its predecessor: the same query, record, strand, start and end -- two windows found one copy
+__global__ __launch_bounds__(SCR_TPB) void k_hit_dups(uint64_t base, uint64_t end, LociPtrs l, uint32_t *__restrict__ dup)
+{
+    const uint64_t j = base + (uint64_t)blockIdx.x * SCR_TPB + threadIdx.x;
+    if (j >= end) return;
+    const bool same = j > 0 && l.f[LF_QUERY][j] == l.f[LF_QUERY][j - 1] && l.f[LF_RECORD][j] == l.f[LF_RECORD][j - 1] &&
+                      l.f[LF_STRAND][j] == l.f[LF_STRAND][j - 1] && l.f[LF_START][j] == l.f[LF_START][j - 1] && l.f[LF_END][j] == l.f[LF_END][j - 1];
+    dup[j] = same ? 1u : 0u;
+}
+
+// a thread per cell over its contiguous segment: no atomics, so nothing depends on an order
+__global__ __launch_bounds__(SCR_TPB) void k_loci_reduce(uint64_t base, uint64_t end, const uint64_t *__restrict__ cell_off, const uint32_t *__restrict__ dup,
+                                                         const uint32_t *__restrict__ nident, uint32_t *__restrict__ n_loci, uint32_t *__restrict__ sum_nident)
+{
+    const uint64_t c = base + (uint64_t)blockIdx.x * SCR_TPB + threadIdx.x;
+    if (c >= end) return;
+    uint32_t n = 0, s = 0;
+    for (uint64_t j = cell_off[c]; j < cell_off[c + 1]; ++j)
+        if (!dup[j]) {
+            ++n;
+            s += nident[j];
+        }
+    n_loci[c] = n;
+    sum_nident[c] = s;
+}
+
+struct LociChunk {
+    uint64_t n = 0;
+    DevArray<uint32_t> f[LF_CHUNK];
+    LociPtrs ptrs() const
+    {
+        LociPtrs p;
+        for (int i = 0; i < LF_CHUNK; ++i) p.f[i] = f[i].p;
+        return p;
+    }
+};
+
+struct AsU64 {
+    __host__ __device__ uint64_t operator()(uint32_t x) const { return x; }
+};
+
+// the chunks' lists into the final order (query, assembly, record, orientation, band), duplicates, and the per-cell reduction
+void finish_loci(std::vector<LociChunk> &chunks, uint64_t nq, uint64_t n_asm, uint64_t max_q, hipStream_t stream, HitLoci &L)
+{
+    const uint64_t n_cells = nq * n_asm;
+    uint64_t total = 0;
+    for (const LociChunk &c : chunks) total += c.n;
+    L.n = total;
+    L.cell_off.alloc(n_cells + 1);
+    L.n_loci.alloc(n_cells);
+    L.sum_nident.alloc(n_cells);
+    for (int f = 0; f < LOCI_LIST_FIELDS; ++f) L.f[f].alloc(total);
+    if (!total) {
+        SW_HIP(hipMemsetAsync(L.cell_off.p, 0, (n_cells + 1) * 8, stream));
+        if (n_cells) {
+            SW_HIP(hipMemsetAsync(L.n_loci.p, 0, n_cells * 4, stream));
+            SW_HIP(hipMemsetAsync(L.sum_nident.p, 0, n_cells * 4, stream));
+        }
+        SW_HIP(hipStreamSynchronize(stream));
+        return;
+    }
+    DevArray<uint64_t> first(n_cells), past(n_cells);
+    SW_HIP(hipMemsetAsync(first.p, 0, n_cells * 8, stream));
+    SW_HIP(hipMemsetAsync(past.p, 0, n_cells * 8, stream));
+    uint64_t g0 = 0;
+    for (const LociChunk &c : chunks) {
+        launch_1d(k_loci_bounds, c.n, stream, (const uint32_t *)c.f[LF_QUERY].p, (const uint32_t *)c.f[LF_ASM].p, c.n, g0, n_asm, first.p, past.p);
+        g0 += c.n;
+    }
+    {
+        size_t tmp_bytes = 0;
+        auto in = rocprim::make_transform_iterator(rocprim::make_counting_iterator<uint64_t>(0), CellCount{first.p, past.p, n_cells});
+        SW_HIP(rocprim::exclusive_scan(nullptr, tmp_bytes, in, L.cell_off.p, uint64_t(0), n_cells + 1, rocprim::plus<uint64_t>(), stream));
+        DevArray<unsigned char> tmp(tmp_bytes);
+        SW_HIP(rocprim::exclusive_scan(tmp.p, tmp_bytes, in, L.cell_off.p, uint64_t(0), n_cells + 1, rocprim::plus<uint64_t>(), stream));
+        SW_HIP(hipStreamSynchronize(stream));
+    }
+    LociPtrs out;
+    for (int f = 0; f < LF_CHUNK; ++f) out.f[f] = L.f[f].p;
+    g0 = 0;
+    for (LociChunk &c : chunks) {
+        launch_1d(k_loci_gather, c.n, stream, c.ptrs(), g0, n_asm, (const uint64_t *)first.p, (const uint64_t *)L.cell_off.p, out);
+        g0 += c.n;
+    }
+    launch_1d(k_hit_dups, total, stream, out, L.f[LF_DUP].p);
+    launch_1d(k_loci_reduce, n_cells, stream, (const uint64_t *)L.cell_off.p, (const uint32_t *)L.f[LF_DUP].p, (const uint32_t *)L.f[LF_NIDENT].p, L.n_loci.p,
+              L.sum_nident.p);
+    // the largest cell and the loci that are no duplicates
+    DevArray<uint64_t> d_red(2);
+    uint64_t red[2] = {};
+    {
+        size_t tmp_bytes = 0;
+        auto in = rocprim::make_transform_iterator((const uint32_t *)L.n_loci.p, AsU64{});
+        SW_HIP(rocprim::reduce(nullptr, tmp_bytes, in, d_red.p, uint64_t(0), n_cells, rocprim::maximum<uint64_t>(), stream));
+        DevArray<unsigned char> tmp(tmp_bytes);
+        SW_HIP(rocprim::reduce(tmp.p, tmp_bytes, in, d_red.p, uint64_t(0), n_cells, rocprim::maximum<uint64_t>(), stream));
+        SW_HIP(rocprim::reduce(tmp.p, tmp_bytes, in, d_red.p + 1, uint64_t(0), n_cells, rocprim::plus<uint64_t>(), stream));
+        SW_HIP(hipMemcpyAsync(red, d_red.p, 16, hipMemcpyDeviceToHost, stream));
+        SW_HIP(hipStreamSynchronize(stream));   // (the chunks' lists and the scratch are read until here)
+    }
+    L.max_per_cell = red[0];
+    L.n_dup = total - red[1];
+    if (L.max_per_cell * max_q >= (1ull << 32))
+        raise(SW_ERR_VALUE, "best hits: %llu loci in one cell times the longest query (%llu) do not fit the 32-bit sum of nident", (unsigned long long)L.max_per_cell,
+              (unsigned long long)max_q);
+}
+
 }  // namespace
 }  // namespace sw
 
 namespace sw {
 namespace {
 
-// align: the traceback of every chunk's winners (align.hip) right behind their distances, while the chunk's windows exist
-void batch_best_hits(const sw_batch &b, const uint64_t *offsets, const char *blob, uint64_t nq, uint32_t k, bool align, sw_hits &o)
+// align: the traceback of every chunk's winners (align.hip) right behind their distances, while the chunk's windows exist.
+// min_seeds > 0: the loci mode (it implies align) -- behind the winners of a chunk, every locus of the chunk's runs is listed,
+// measured and traced the same way; after the last chunk the lists are ordered and reduced per cell (finish_loci)
+void batch_best_hits(const sw_batch &b, const uint64_t *offsets, const char *blob, uint64_t nq, uint32_t k, bool align, uint64_t min_seeds, sw_hits &o)
 {
+    const bool loci = min_seeds > 0;
+    std::vector<LociChunk> loci_chunks;
     const hipStream_t stream = HIT_STREAM;
     const HostBatch &h = b.host;
     const uint64_t n_asm = h.n_assemblies, n_cells = nq * n_asm;
@@ -488,6 +695,8 @@ void batch_best_hits(const sw_batch &b, const uint64_t *offsets, const char *blo
         if (n_cells) SW_HIP(hipMemsetAsync(o.field[f].p, (f == 0 || f == 2) ? 0 : 0xFF, n_cells * 4, stream));
     }
     o.aligned = align;
+    o.has_loci = loci;
+    o.loci.min_seeds = min_seeds;
     if (align)
         for (int f = 0; f < 4; ++f) {
             o.afield[f].alloc(n_cells);
@@ -647,11 +856,48 @@ void batch_best_hits(const sw_batch &b, const uint64_t *offsets, const char *blo
                     uint32_t *const out[4] = {o.afield[0].p, o.afield[1].p, o.afield[2].p, o.afield[3].p};
                     align_device(runs_of(runs.t), P, pairs.p, out_idx.p, n_pairs, o.field[4].p, o.field[3].p, out, nullptr, nullptr, o.align);
                 }
+                if (loci) {
+                    // every locus of the chunk's runs: peaks, their list, then Layer A and the traceback as for the winners
+                    Event l0, l1;
+                    SW_HIP(hipEventRecord(l0, stream));
+                    DevArray<uint8_t> peak(n_runs_k);
+                    DevArray<uint32_t> peak_at(n_runs_k + 1);
+                    launch_1d(k_hit_peaks, n_runs_k, stream, (const uint64_t *)ukey.p, (const uint32_t *)upos.p, n_runs_k, (uint64_t)n_hits, band_bits, min_seeds, peak.p);
+                    LociChunk lc;
+                    lc.n = scan_flags(peak.p, peak_at.p, n_runs_k, stream);
+                    for (int f = 0; f < LF_CHUNK; ++f) lc.f[f].alloc(lc.n);
+                    DevArray<sw_infix_pair> lpairs(lc.n);
+                    launch_1d(k_hit_loci, n_runs_k, stream, (const uint8_t *)peak.p, (const uint32_t *)peak_at.p, (const uint64_t *)ukey.p, (const uint32_t *)upos.p,
+                              n_runs_k, (uint64_t)n_hits, (const uint64_t *)P.off.p, (const uint32_t *)runs.t.rec_len, (const uint32_t *)b.d_rec_asm.p, k, band_bits,
+                              rec_bits, lc.ptrs(), lpairs.p);
+                    SW_HIP(hipEventRecord(l1, stream));
+                    SW_HIP(hipStreamSynchronize(stream));
+                    SW_HIP(hipEventElapsedTime(&fms, l0, l1));
+                    o.loci.ms[0] += fms;
+                    uint64_t lcn[6] = {};
+                    double lms[1] = {};
+                    infix_device(runs_of(runs.t), P, lpairs.p, nullptr, lc.n, lc.f[LF_DIST].p, lc.f[LF_END].p, lcn, lms);
+                    o.loci.ms[1] += lms[0];
+                    o.loci.aligned += lcn[0];
+                    uint32_t *const lout[4] = {lc.f[LF_START].p, lc.f[LF_NIDENT].p, lc.f[LF_MISMATCH].p, lc.f[LF_GAPS].p};
+                    align_device(runs_of(runs.t), P, lpairs.p, nullptr, lc.n, lc.f[LF_DIST].p, lc.f[LF_END].p, lout, nullptr, nullptr, o.loci.align);
+                    if (lc.n) loci_chunks.push_back(std::move(lc));
+                }
             }
             a0 = a1;
         }
     }
     SW_HIP(hipStreamSynchronize(stream));
+    if (loci) {
+        Event f0, f1;
+        SW_HIP(hipEventRecord(f0, stream));
+        finish_loci(loci_chunks, nq, n_asm, max_q, stream, o.loci);
+        SW_HIP(hipEventRecord(f1, stream));
+        SW_HIP(hipStreamSynchronize(stream));
+        SW_HIP(hipEventElapsedTime(&fms, f0, f1));
+        o.loci.ms[3] = fms;
+        o.loci.ms[2] = o.loci.align.ms[0] + o.loci.align.ms[1];
+    }
     const uint64_t cn[10] = {hits, n_seeds_total, chunks, splits, launches, aligned, striped, Q.n_distinct, cap_keys, grows};
     memcpy(o.counters, cn, sizeof cn);
 }
@@ -680,9 +926,12 @@ void check_infix_pairs(const char *what, const sw_batch *b, const uint64_t *offs
 
 namespace {
 
-void best_hits_entry(const sw_batch *batch, const uint64_t *offsets, const char *blob, uint64_t n_queries, uint64_t k, bool align, sw_hits **out)
+// min_seeds: nullptr without the loci mode
+void best_hits_entry(const sw_batch *batch, const uint64_t *offsets, const char *blob, uint64_t n_queries, uint64_t k, bool align, const uint64_t *min_seeds,
+                     sw_hits **out)
 {
     if (k < 1 || k > 32) raise(SW_ERR_VALUE, "best hits: k-mer length must lie in 1..32 (got %llu)", (unsigned long long)k);
+    if (min_seeds && !*min_seeds) raise(SW_ERR_VALUE, "best hits: min_seeds must be at least 1 (got 0)");
     if (!batch || !out) raise(SW_ERR_VALUE, "best hits: a NULL handle or array");
     check_queries("best hits", offsets, blob, n_queries);
     if (batch->host.rec_len.size() && !batch->d_packed.p) raise(SW_ERR_VALUE, "best hits: the batch holds no packed bases (it must be resident)");
@@ -690,7 +939,7 @@ void best_hits_entry(const sw_batch *batch, const uint64_t *offsets, const char 
     StreamScope scope(HIT_STREAM);
     std::unique_ptr<sw_hits> o(new sw_hits);
     o->device = batch->device;
-    batch_best_hits(*batch, offsets, blob, n_queries, (uint32_t)k, align, *o);
+    batch_best_hits(*batch, offsets, blob, n_queries, (uint32_t)k, align, min_seeds ? *min_seeds : 0, *o);
     *out = o.release();
 }
 
@@ -726,12 +975,72 @@ int sw_batch_infix_distances(const sw_batch *b, const uint64_t *offsets, const c
 
 int sw_batch_best_hits(const sw_batch *batch, const uint64_t *offsets, const char *blob, uint64_t n_queries, uint64_t k, sw_hits **out)
 {
-    return guarded([&] { best_hits_entry(batch, offsets, blob, n_queries, k, false, out); });
+    return guarded([&] { best_hits_entry(batch, offsets, blob, n_queries, k, false, nullptr, out); });
 }
 
 int sw_batch_best_hits_aligned(const sw_batch *batch, const uint64_t *offsets, const char *blob, uint64_t n_queries, uint64_t k, sw_hits **out)
 {
-    return guarded([&] { best_hits_entry(batch, offsets, blob, n_queries, k, true, out); });
+    return guarded([&] { best_hits_entry(batch, offsets, blob, n_queries, k, true, nullptr, out); });
+}
+
+int sw_batch_best_hits_loci(const sw_batch *batch, const uint64_t *offsets, const char *blob, uint64_t n_queries, uint64_t k, uint64_t min_seeds, sw_hits **out)
+{
+    return guarded([&] { best_hits_entry(batch, offsets, blob, n_queries, k, true, &min_seeds, out); });
+}
+
+static const sw_hits &loci_of(const sw_hits *h)
+{
+    if (!h) raise(SW_ERR_VALUE, "best hits: a NULL handle");
+    if (!h->has_loci) raise(SW_ERR_VALUE, "best hits: these hits were made without the loci (sw_batch_best_hits_loci makes them)");
+    return *h;
+}
+
+int sw_hits_loci_sizes(const sw_hits *h, uint64_t *n_loci_total, uint64_t *n_dup)
+{
+    return guarded([&] {
+        const HitLoci &l = loci_of(h).loci;
+        if (n_loci_total) *n_loci_total = l.n;
+        if (n_dup) *n_dup = l.n_dup;
+    });
+}
+
+int sw_hits_loci(const sw_hits *h, uint64_t *cell_offsets, uint32_t *query, uint32_t *assembly, uint32_t *record, uint32_t *strand, uint32_t *band, uint32_t *seeds,
+                 uint32_t *dist, uint32_t *end, uint32_t *a_start, uint32_t *nident, uint32_t *mismatch, uint32_t *gaps, uint32_t *dup)
+{
+    return guarded([&] {
+        const HitLoci &l = loci_of(h).loci;
+        require_device(h->device, "the hits");
+        if (cell_offsets) SW_HIP(hipMemcpy(cell_offsets, l.cell_off.p, (h->nq * h->n_asm + 1) * 8, hipMemcpyDeviceToHost));
+        uint32_t *const out[LOCI_LIST_FIELDS] = {query, assembly, record, strand, band, seeds, dist, end, a_start, nident, mismatch, gaps, dup};
+        for (int f = 0; f < LOCI_LIST_FIELDS; ++f)
+            if (out[f] && l.n) SW_HIP(hipMemcpy(out[f], l.f[f].p, l.n * 4, hipMemcpyDeviceToHost));
+    });
+}
+
+int sw_hits_loci_block(const sw_hits *h, uint64_t field, uint64_t r0, uint64_t r1, uint64_t c0, uint64_t c1, uint32_t *out)
+{
+    return guarded([&] {
+        const HitLoci &l = loci_of(h).loci;
+        if (field > 1) raise(SW_ERR_VALUE, "best hits: field %llu is none of n_loci, sum_nident (0..1)", (unsigned long long)field);
+        if (r0 > r1 || r1 > h->nq || c0 > c1 || c1 > h->n_asm)
+            raise(SW_ERR_VALUE, "best hits: rows [%llu, %llu) x columns [%llu, %llu) lie outside the %llu queries x %llu assemblies", (unsigned long long)r0,
+                  (unsigned long long)r1, (unsigned long long)c0, (unsigned long long)c1, (unsigned long long)h->nq, (unsigned long long)h->n_asm);
+        const uint64_t nr = r1 - r0, nc = c1 - c0;
+        if (!nr || !nc) return;
+        if (!out) raise(SW_ERR_VALUE, "best hits: a NULL handle or array");
+        require_device(h->device, "the hits");
+        SW_HIP(hipMemcpy2D(out, nc * 4, (field ? l.sum_nident.p : l.n_loci.p) + r0 * h->n_asm + c0, h->n_asm * 4, nc * 4, nr, hipMemcpyDeviceToHost));
+    });
+}
+
+int sw_hits_loci_stats(const sw_hits *h, uint64_t *counters, double *ms)
+{
+    return guarded([&] {
+        const HitLoci &l = loci_of(h).loci;
+        const uint64_t cn[5] = {l.n, l.n_dup, l.max_per_cell, l.aligned, l.align.counters[1]};
+        if (counters) memcpy(counters, cn, sizeof cn);
+        if (ms) memcpy(ms, l.ms, sizeof l.ms);
+    });
 }
 
 int sw_hits_sizes(const sw_hits *h, uint64_t *n_queries, uint64_t *n_assemblies, uint64_t *n_seeds, uint64_t *k)

@@ -24,6 +24,18 @@ struct AlignStats {
     double ms[2] = {};
 };
 
+// Every seeded locus of a call made in loci mode, in the list's final order (query, record, strand, band).
+// counters-to-be: n, n_dup, max_per_cell, aligned; ms[4] = { peaks + compact, distances, traceback, final ordering + reduction }
+constexpr int LOCI_LIST_FIELDS = 13;   // query, assembly, record, strand, band, seeds, dist, end, start, nident, mismatch, gaps, dup
+struct HitLoci {
+    uint64_t n = 0, n_dup = 0, max_per_cell = 0, aligned = 0, min_seeds = 0;
+    DevArray<uint32_t> f[LOCI_LIST_FIELDS];   // [n] each
+    DevArray<uint64_t> cell_off;              // [nq * n_asm + 1]
+    DevArray<uint32_t> n_loci, sum_nident;    // [nq][n_asm]
+    AlignStats align;                         // the loci's traceback (the winners' own stays in sw_hits::align)
+    double ms[4] = {};
+};
+
 // RunTable (seqs_core.hpp) has internal linkage like every type of that header; this is the same table as the two files hand it to
 // each other (runs_of / table_of below)
 struct Runs {
@@ -78,4 +90,6 @@ struct sw_hits {
     bool aligned = false;                          // made by sw_batch_best_hits_aligned
     sw::DevArray<uint32_t> afield[4];              // [nq][n_asm] a_start, nident, mismatch, gaps (aligned only)
     sw::AlignStats align;
+    bool has_loci = false;                         // made by sw_batch_best_hits_loci
+    sw::HitLoci loci;
 };

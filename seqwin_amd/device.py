@@ -184,16 +184,25 @@ class Batch:
             res += (d,)
         return res
 
-    def best_hits(self, queries, kmerlen: int, align: bool = False) -> "BestHits":
+    def best_hits(self, queries, kmerlen: int, align: bool = False, loci: bool = False, min_seeds: int = 1) -> "BestHits":
         """For every query (a list of ``str`` or ``bytes``) and every assembly: the best seeded locus and the exact infix edit
         distance of the query to the best substring there (csrc/hits.hip).  A seed is a canonical
         ``kmerlen``-mer that exactly one window of ALL the query text has and that is not its own reverse complement: a query whose
         k-mers are shared with another query, or repeat inside it, loses them as seeds -- deliberately, one hit means one diagonal.
         Not BLAST: no scores, no e-values, no local alignment, one locus per pair.  ValueError for a k-mer length outside 1..32.
         ``align=True`` also traces every winner's alignment (:meth:`infix_alignments` on its window): the result then answers
-        ``start()``, ``nident()``, ``mismatch()``, ``gaps()`` and ``intervals()``."""
+        ``start()``, ``nident()``, ``mismatch()``, ``gaps()`` and ``intervals()``.
+        ``loci=True`` (it implies ``align=True``) also lists EVERY seeded locus of every pair with ``min_seeds`` or more seeds (DESIGN.md
+        section 3.2g: a local maximum of the vote over two bands to either side), each measured and traced like a winner: the result
+        then answers ``n_loci()``, ``sum_nident()``, ``loci()``, ``loci_intervals()`` and ``loci_stats()``.  The matrix fields do not
+        depend on ``min_seeds``.  ValueError for ``min_seeds < 1``.  Still not BLAST."""
         offs, blob, nq = _query_csr(queries)
         h = c_vp()
+        if loci:
+            if int(min_seeds) < 1:
+                raise ValueError(f"min_seeds must be at least 1 (got {min_seeds})")
+            check(lib.sw_batch_best_hits_loci(self._h, _ptr(offs), blob, c_u64(nq), c_u64(int(kmerlen)), c_u64(int(min_seeds)), ctypes.byref(h)))
+            return BestHits(h, aligned=True, loci=True)
         fn = lib.sw_batch_best_hits_aligned if align else lib.sw_batch_best_hits
         check(fn(self._h, _ptr(offs), blob, c_u64(nq), c_u64(int(kmerlen)), ctypes.byref(h)))
         return BestHits(h, aligned=bool(align))
@@ -638,12 +647,12 @@ class Markers:
         o = offs.astype(np.int64)
         return batch.screen([blob[o[i]:o[i + 1]] for i in range(len(o) - 1)], kmerlen)
 
-    def best_hits(self, batch: "Batch", kmerlen: int, select=None, align: bool = False) -> "BestHits":
+    def best_hits(self, batch: "Batch", kmerlen: int, select=None, align: bool = False, loci: bool = False, min_seeds: int = 1) -> "BestHits":
         """:meth:`Batch.best_hits` of the representatives' text -- ``sequences(batch, "reps", select)``, in that order -- against
         every assembly of ``batch``.  ``kmerlen`` is the caller's choice; it need not be the graph's k."""
         offs, blob, _ = self.sequences(batch, "reps", select)
         o = offs.astype(np.int64)
-        return batch.best_hits([blob[o[i]:o[i + 1]] for i in range(len(o) - 1)], kmerlen, align=align)
+        return batch.best_hits([blob[o[i]:o[i + 1]] for i in range(len(o) - 1)], kmerlen, align=align, loci=loci, min_seeds=min_seeds)
 
     def candidates(self, min_len: int) -> np.ndarray:
         """Indices of the subgraphs the reference keeps (markers.py:514-517): len >= min_len, neither single nor dup."""
@@ -852,6 +861,9 @@ class Screen:
             pass
 
 
+LOCI_FIELDS = ("query", "assembly", "record", "strand", "band", "seeds", "dist", "end", "start", "nident", "mismatch", "gaps", "dup")
+
+
 class BestHits:
     """The best hit of every query in every assembly of a batch, resident on the device (:meth:`Batch.best_hits`,
     :meth:`Markers.best_hits`; csrc/hits.hip): per (query, assembly) the winning locus' vote ``seeds``, its
@@ -860,11 +872,14 @@ class BestHits:
     of ``eval_markers`` (src/seqwin/markers.py:607-696), has no counterpart in the reference, is not BLAST and fills none of
     ``MarkerMetrics``.  A single-device object on a resident batch.  ``rows`` (queries) / ``cols`` (assemblies) are None (all), a
     ``(lo, hi)`` pair, a slice or a range.  Made with ``align=True`` it also holds the canonical alignment of every hit (csrc/align.hip,
-    DESIGN.md section 3.2f): ``start``, ``nident``, ``mismatch`` and ``gaps``, NO_HIT where there is no hit."""
+    DESIGN.md section 3.2f): ``start``, ``nident``, ``mismatch`` and ``gaps``, NO_HIT where there is no hit.  Made with ``loci=True`` it
+    also holds every seeded locus of every pair: the list ``loci()`` and, per pair, ``n_loci`` and
+    ``sum_nident`` over the loci that are no duplicates -- counts, 0 where there is none."""
 
-    def __init__(self, handle: c_vp, aligned: bool = False):
+    def __init__(self, handle: c_vp, aligned: bool = False, loci: bool = False):
         self._h = handle
         self._aligned = aligned
+        self._loci = loci
 
     def sizes(self):
         """(queries, assemblies, seeds of all queries, k)"""
@@ -944,6 +959,58 @@ class BestHits:
         check(lib.sw_hits_align_stats(self._h, c, ms))
         d = dict(zip(_ALIGN_COUNTERS, (int(x) for x in c)))
         d.update(store_ms=ms[0], walk_ms=ms[1])
+        return d
+
+    def _loci_block(self, field: int, rows, cols) -> np.ndarray:
+        if not self._loci:
+            raise ValueError("these best hits were made without loci=True")
+        nq, na, _, _ = self.sizes()
+        (r0, r1), (c0, c1) = _block_range(rows, nq), _block_range(cols, na)
+        out = np.empty((max(r1 - r0, 0), max(c1 - c0, 0)), np.uint32)
+        check(lib.sw_hits_loci_block(self._h, c_u64(field), c_u64(r0), c_u64(r1), c_u64(c0), c_u64(c1), _ptr(out)))
+        return out
+
+    def n_loci(self, rows=None, cols=None) -> np.ndarray:
+        """uint32[rows, cols]: the pair's loci with ``min_seeds`` or more seeds, duplicates counted once; 0: none."""
+        return self._loci_block(0, rows, cols)
+
+    def sum_nident(self, rows=None, cols=None) -> np.ndarray:
+        """uint32[rows, cols]: the sum of ``nident`` over the loci ``n_loci`` counts."""
+        return self._loci_block(1, rows, cols)
+
+    def loci(self) -> dict:
+        """The list of all loci, ascending by (query, record, strand, band), as parallel arrays: ``query``, ``assembly``, ``record``,
+        ``strand``, ``band``, ``seeds``, ``dist``, ``end``, ``start``, ``nident``, ``mismatch``, ``gaps`` and ``dup`` (1: the locus
+        before it is the same copy); ``cell_offsets`` (uint64[queries * assemblies + 1]) bounds the loci of every pair."""
+        if not self._loci:
+            raise ValueError("these best hits were made without loci=True")
+        nq, na, _, _ = self.sizes()
+        n, nd = c_u64(), c_u64()
+        check(lib.sw_hits_loci_sizes(self._h, ctypes.byref(n), ctypes.byref(nd)))
+        offs = np.empty(nq * na + 1, np.uint64)
+        cols = [np.empty(n.value, np.uint32) for _ in LOCI_FIELDS]
+        check(lib.sw_hits_loci(self._h, _ptr(offs), *[_ptr(a) if n.value else None for a in cols]))
+        out = {f: (a.astype(np.uint8) if f in ("strand", "dup") else a) for f, a in zip(LOCI_FIELDS, cols)}
+        out["cell_offsets"] = offs
+        return out
+
+    def loci_intervals(self) -> np.ndarray:
+        """INTERVAL_DTYPE ``(record, start, end)`` of every locus that is no duplicate, in the list's order, as :meth:`Batch.fetch`
+        takes them."""
+        L = self.loci()
+        keep = L["dup"] == 0
+        iv = np.empty(int(keep.sum()), INTERVAL_DTYPE)
+        iv["record"], iv["start"], iv["stop"] = L["record"][keep], L["start"][keep], L["end"][keep]
+        return iv
+
+    def loci_stats(self) -> dict:
+        if not self._loci:
+            raise ValueError("these best hits were made without loci=True")
+        c = (c_u64 * 5)()
+        ms = (ctypes.c_double * 4)()
+        check(lib.sw_hits_loci_stats(self._h, c, ms))
+        d = dict(zip(("loci", "duplicates", "max_loci_per_cell", "pairs_aligned", "rounds"), (int(x) for x in c)))
+        d.update(peaks_ms=ms[0], distance_ms=ms[1], traceback_ms=ms[2], order_ms=ms[3])
         return d
 
     def stats(self) -> dict:

@@ -278,6 +278,38 @@ def alignment_summary(h, lengths, n_tar: int) -> np.ndarray:
     return out
 
 
+REPEAT_SUMMARY_DTYPE = np.dtype([("loci_tar", "<f8"), ("identity_all_tar", "<f8"), ("loci_neg", "<f8"), ("identity_all_neg", "<f8")])
+
+
+def repeat_summary(h, lengths, n_tar: int) -> np.ndarray:
+    """Per query of a :class:`BestHits` made with ``loci=True``, with ``lengths`` the queries' lengths, the targets the first
+    ``n_tar`` columns and the non-targets the rest; a cell with ``n_loci > 0`` has a hit.  ``loci_tar`` = the mean of ``n_loci`` over
+    the query's target cells with a hit, ``identity_all_tar`` = the mean of ``sum_nident / n_loci`` over those cells / len;
+    ``loci_neg`` / ``identity_all_neg`` the same over the non-target cells -- the arithmetic ``_get_metrics``
+    (src/seqwin/markers.py:566-604) applies to its ``n_hits`` and ``avg_nident`` columns, here on the seeded loci of DESIGN.md section
+    3.2g.  ``0.0`` where no cell of the group has a hit, as ``_BASELINE_METRICS`` reads.  The names are deliberately not those of
+    ``MarkerMetrics``: a locus is not a BLAST hit, this is not BLAST, and nothing of it is written into ``signatures.csv``."""
+    n_loci = np.asarray(h.n_loci(), np.uint32)
+    sum_nident = np.asarray(h.sum_nident(), np.uint32)
+    lengths = np.asarray(lengths, np.int64).reshape(-1)
+    if n_loci.ndim != 2 or lengths.shape != (n_loci.shape[0],) or (lengths < 0).any():
+        raise ValueError(f"hits of shape {n_loci.shape} against {lengths.shape} query lengths")
+    n_tar = int(n_tar)
+    if not 0 <= n_tar <= n_loci.shape[1]:
+        raise ValueError(f"n_tar = {n_tar} lies outside the {n_loci.shape[1]} assemblies")
+    out = np.zeros(len(lengths), REPEAT_SUMMARY_DTYPE)
+    hit = n_loci > 0
+    avg = np.where(hit, sum_nident / np.maximum(n_loci, 1), 0.0)      # (a cell with a hit has a query of at least k bases)
+    ln = np.maximum(lengths, 1).astype(np.float64)
+    for loci_name, ident_name, cols in (("loci_tar", "identity_all_tar", slice(0, n_tar)), ("loci_neg", "identity_all_neg", slice(n_tar, None))):
+        cells = hit[:, cols].sum(axis=1)
+        some = cells > 0
+        den = np.maximum(cells, 1)
+        out[loci_name] = np.where(some, np.where(hit, n_loci, 0)[:, cols].sum(axis=1) / den, 0.0)
+        out[ident_name] = np.where(some, avg[:, cols].sum(axis=1) / den / ln, 0.0)
+    return out
+
+
 def cigar(offsets, ops) -> list:
     """The edit scripts of :meth:`Batch.infix_alignments` (``ops=True``) as run-length strings such as ``12=1X3=2I``: ``=`` match,
     ``X`` mismatch, ``I`` a query base facing a gap, ``D`` a text base facing a gap; an empty script is the empty string."""
