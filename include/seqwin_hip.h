@@ -579,6 +579,23 @@ int sw_hits_loci_block(const sw_hits *h, uint64_t field, uint64_t r0, uint64_t r
  * the first three summed over the chunks). */
 int sw_hits_loci_stats(const sw_hits *h, uint64_t *counters, double *ms);
 
+/* ---- seeds shared between queries, up to a cap of copies (csrc/hits.hip, k_hit_probe_shared) --------------------------------------
+ * By DESIGN.md section 3.2h (tests/tools/shared_seeds_host.py restates it).  mult(word) = the valid windows of ALL query text whose
+ * canonical word it is.  With seed_copies = c: a word is a seed iff 1 <= mult <= c and it is not its own reverse complement, and
+ * every one of its windows (query, offset, window-is-canonical) owns it; a word with mult > c is dropped whole.  n_seeds[q] counts
+ * the windows of q that own a seed.  A window of the batch whose word is a seed is one hit per owner, each by Layer B's formulas with
+ * that owner's query, offset and orientation; from the hits on -- vote, ties, winners, windows, distances, alignments, loci --
+ * everything is Layer B's.  At c = 1 every output equals the corresponding call above bit for bit.
+ * mode: 0 as sw_batch_best_hits, 1 as sw_batch_best_hits_aligned, 2 as sw_batch_best_hits_loci; min_seeds is read in mode 2 only.
+ * The result answers every sw_hits_* call its mode's call answers.  seed_copies outside 1..256, a mode above 2, min_seeds == 0 in
+ * mode 2 (all checked before a device is touched), more than 2^31 queries -> SW_ERR_VALUE; the rest as sw_batch_best_hits. */
+int sw_batch_best_hits_shared(const sw_batch *batch, const uint64_t *offsets, const char *blob, uint64_t n_queries, uint64_t k, uint64_t seed_copies,
+                              uint64_t mode, uint64_t min_seeds, sw_hits **out);
+/* counters[8] = { seed_copies (0: made by one of the calls above, whose rule is the one at c = 1), seed words kept, windows that own
+ * them, words dropped for mult > c, the windows dropped with them, words that are their own reverse complement (whatever their
+ * mult; they are not counted as dropped), the longest owner list, hits appended over all chunks }. */
+int sw_hits_seed_stats(const sw_hits *h, uint64_t *counters);
+
 /* ---- multi-GPU merge (one process per GPU; the exchange itself is done by the host side with
  *      torch.distributed / RCCL on the device buffers below).  Together these replace
  *      merge_thread_graphs (cpp/src/seqwin/build_internals.cpp:295-392) across GPUs. -------------- */

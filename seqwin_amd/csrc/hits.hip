@@ -24,6 +24,11 @@
 //   run that is a local maximum of the score over two bands to either side (k_hit_peaks) is listed (k_hit_loci), measured and traced
 //   like a winner; after the last chunk the lists are gathered into (query, record, orientation, band) order (k_loci_bounds, a scan,
 //   k_loci_gather), duplicates are marked (k_hit_dups) and every cell is reduced by one thread (k_loci_reduce).
+// Shared seeds (sw_batch_best_hits_shared; tests/tools/shared_seeds_host.py restates it): a word that up to
+//   `seed_copies` windows of the query text have is a seed owned by each of them.  k_hit_keep (what the cap keeps, and the counts
+//   of sw_hits_seed_stats), a scan, k_own_keys + a sort + k_own_fill (owner lists as CSR over the distinct words, placed by rank in
+//   the sorted windows: no atomic decides a place), k_hit_probe_shared (a key per owner of a window's word: owners summed, one
+//   append per wave, then the lists walked).  Everything behind the probe is the code above.
 #include "hits_core.hpp"
 
 namespace sw {
@@ -357,6 +362,86 @@ __global__ __launch_bounds__(SCR_TPB) void k_hit_seeds(uint64_t base, uint64_t e
     atomicAdd(n_seeds + q, 1u);
 }
 
+// ---- Layer B: shared seeds -----------------------------------------------------------------------------
+// A word that 1 .. c windows of all query text have, and that is not its own reverse complement, is a seed that every one of those
+// windows owns.  Both routes count what that rule keeps and drops (sw_hits_seed_stats); the unique route is the rule at c = 1.
+enum { SS_WORDS, SS_OCC, SS_DROPPED_WORDS, SS_DROPPED_OCC, SS_PALINDROMES, SS_LONGEST, SS_N };
+
+__device__ __forceinline__ bool own_revcomp(uint64_t word, uint32_t k)
+{
+    uint64_t rc = 0, x = word;
+    for (uint32_t i = 0; i < k; ++i) {
+        rc = (rc << 2) | (3 - (x & 3));
+        x >>= 2;
+    }
+    return rc == word;
+}
+
+// distinct word id: kept[id] = its windows if it is a seed under the cap c, else 0 (kept == nullptr: only the counts are taken).
+// A palindromic word counts as that, whatever its windows; a dropped word is a non-palindromic one above the cap
+__global__ __launch_bounds__(SCR_TPB) void k_hit_keep(uint64_t base, uint64_t end, const uint32_t *__restrict__ mult, const uint64_t *__restrict__ by_number, uint32_t k,
+                                                      uint32_t c, uint32_t *__restrict__ kept, unsigned long long *__restrict__ stat)
+{
+    const uint64_t id = base + (uint64_t)blockIdx.x * SCR_TPB + threadIdx.x;
+    uint32_t m = 0, keep = 0, pal = 0;
+    if (id < end) {
+        m = mult[id];
+        pal = own_revcomp(by_number[id], k) ? 1u : 0u;
+        keep = (!pal && m <= c) ? m : 0u;
+        if (kept) kept[id] = keep;
+    }
+    const uint32_t dropped = (!pal && m > c) ? m : 0u;
+    const unsigned long long words = wave_sum(keep ? 1 : 0), occ = wave_sum(keep), d_words = wave_sum(dropped ? 1 : 0), d_occ = wave_sum(dropped),
+                             pals = wave_sum(pal);
+    const uint32_t longest = wave_max(keep);
+    if (threadIdx.x % SCR_WAVE == 0) {
+        if (words) atomicAdd(stat + SS_WORDS, words);
+        if (occ) atomicAdd(stat + SS_OCC, occ);
+        if (d_words) atomicAdd(stat + SS_DROPPED_WORDS, d_words);
+        if (d_occ) atomicAdd(stat + SS_DROPPED_OCC, d_occ);
+        if (pals) atomicAdd(stat + SS_PALINDROMES, pals);
+        if (longest) atomicMax(stat + SS_LONGEST, (unsigned long long)longest);
+    }
+}
+
+struct KeptAt {
+    const uint32_t *c;
+    uint64_t n;
+    __host__ __device__ uint32_t operator()(uint64_t i) const { return i < n ? c[i] : 0u; }
+};
+
+// valid window j as (its word's number << 32 | j): sorted, a word's windows lie together in text order
+__global__ __launch_bounds__(SCR_TPB) void k_own_keys(uint64_t base, uint64_t end, const uint32_t *__restrict__ sidx, const uint32_t *__restrict__ number,
+                                                      uint64_t *__restrict__ okey)
+{
+    const uint64_t j = base + (uint64_t)blockIdx.x * SCR_TPB + threadIdx.x;
+    if (j < end) okey[j] = ((uint64_t)number[sidx[j]] << 32) | j;
+}
+
+// An owner record: window-is-canonical << 63 | query << 32 | offset in the query (a query index takes 31 bits here).
+// Placement: entry s of the sorted (number, window) keys is the owner of rank (s - the first entry of its number) in its word's
+// list, so a list holds its windows in text order -- no atomic decides a place.  The rank is counted backwards over at most c - 1
+// entries.  n_seeds counts the owners of every query (integer adds: the sum does not depend on their order)
+__global__ __launch_bounds__(SCR_TPB) void k_own_fill(uint64_t base, uint64_t end, const uint64_t *__restrict__ okey, const uint32_t *__restrict__ kept,
+                                                      const uint32_t *__restrict__ occ_off, const uint64_t *__restrict__ by_number, const uint32_t *__restrict__ vpos,
+                                                      const uint8_t *__restrict__ text, const uint64_t *__restrict__ off, uint32_t nq, uint32_t k,
+                                                      uint64_t *__restrict__ owners, uint32_t *__restrict__ n_seeds)
+{
+    const uint64_t s = base + (uint64_t)blockIdx.x * SCR_TPB + threadIdx.x;
+    if (s >= end) return;
+    const uint64_t x = okey[s];
+    const uint32_t id = (uint32_t)(x >> 32), j = (uint32_t)x;
+    if (!kept[id]) return;
+    uint32_t rank = 0;
+    while (rank < s && (uint32_t)(okey[s - rank - 1] >> 32) == id) ++rank;   // (< kept[id] <= c)
+    const uint64_t pos = vpos[j], word = by_number[id];
+    uint64_t fwd = 0;
+    for (uint32_t i = 0; i < k; ++i) fwd = (fwd << 2) | (uint64_t)(base_code(text[pos + i]) & 3u);
+    const uint32_t q = query_of(off, nq, pos);
+    owners[occ_off[id] + rank] = (fwd == word ? 1ull << 63 : 0ull) | ((uint64_t)q << 32) | (pos - off[q]);
+    atomicAdd(n_seeds + q, 1u);
+}
+
 // ---- Layer B: probe -------------------------------------------------------------------------------------------------------------
 struct HitArgs {
     RunView v;                       // with run_rec / run_pos
@@ -425,6 +510,82 @@ __global__ __launch_bounds__(SCR_TPB) void k_hit_probe(HitArgs g)
 #pragma unroll
     for (uint32_t j = 0; j < SCR_L; ++j)
         if ((have >> j) & 1u) g.buf[at++] = key[j];
+}
+
+// The shared-seed probe: k_hit_probe's walk, loads and keys, but a window's word has a list of owners and yields a key per owner.
+// Two steps: the lane's 16 ids are resolved to (first owner, owners) and the owners summed -- one wave_append with the sum, the
+// overflow rule as above --, then the lists are walked and the keys stored.  The loop over the 16 windows is unrolled both times, so
+// beg / len are registers (no array is indexed by a run-time value); the loop over a list has a run-time length and indexes nothing.
+struct HitSharedArgs {
+    RunView v;                       // with run_rec / run_pos
+    Table t;
+    const uint32_t *occ_off;         // [distinct words + 1]: word id's owners are owners[occ_off[id] .. occ_off[id + 1])
+    const uint64_t *owners;          // window-is-canonical << 63 | query << 32 | offset
+    const uint64_t *qoff;
+    uint64_t *buf;
+    uint64_t cap;
+    unsigned long long *cursor;
+    uint32_t k, band_bits, rec_bits;
+};
+
+__global__ __launch_bounds__(SCR_TPB) void k_hit_probe_shared(HitSharedArgs g)
+{
+    if (*(volatile unsigned long long *)g.cursor > g.cap) return;   // (the whole wave: the chunk has overflowed, it is redone anyway)
+    const uint32_t lane = threadIdx.x % SCR_WAVE;
+    uint32_t r, n_mine;
+    uint64_t first;
+    if (!wave_tile(g.v, lane, r, first, n_mine)) return;   // (the whole wave)
+    const uint32_t k = g.k;
+    uint32_t beg[SCR_L], len[SCR_L], is_fwd = 0, cnt = 0, rec = 0;
+    uint64_t p0 = 0;
+#pragma unroll
+    for (uint32_t j = 0; j < SCR_L; ++j) beg[j] = len[j] = 0;
+    if (n_mine) {
+        KmerRoller R(g.v.packed, k);
+        R.start(g.v.run_base[r] + first);
+        for (uint32_t i = 0; i + 1 < k; ++i) R.roll();
+        uint64_t canon[SCR_L];
+        uint32_t home[SCR_L], slot[SCR_L];
+#pragma unroll
+        for (uint32_t j = 0; j < SCR_L; ++j) {
+            canon[j] = 0;
+            if (j < n_mine) {
+                R.roll();
+                canon[j] = R.fwd < R.rev ? R.fwd : R.rev;
+                is_fwd |= (R.fwd < R.rev ? 1u : 0u) << j;
+            }
+        }
+#pragma unroll
+        for (uint32_t j = 0; j < SCR_L; ++j) {   // the 16 first-slot loads leave together
+            home[j] = scr_home(canon[j], g.t.bits);
+            slot[j] = j < n_mine ? g.t.slots[home[j]] : 0u;
+        }
+        rec = g.v.run_rec[r];
+        p0 = (uint64_t)g.v.run_pos[r] + first;
+#pragma unroll
+        for (uint32_t j = 0; j < SCR_L; ++j) {
+            if (!slot[j]) continue;
+            const uint32_t id = scr_find_from(g.t, canon[j], home[j], slot[j]);
+            if (id == SCR_NONE) continue;
+            beg[j] = g.occ_off[id];
+            len[j] = g.occ_off[id + 1] - beg[j];   // (0: the word is no seed)
+            cnt += len[j];                         // (<= 16 * 256)
+        }
+    }
+    const WaveRange w = wave_append(g.cursor, lane, cnt);   // one atomic on the cursor per wave
+    if (!w.total) return;                             // (uniform)
+    if (w.base + w.total > g.cap) return;             // (uniform) overflow: the host reads it from the cursor
+    unsigned long long at = w.base + w.offset;        // the lane writes [at, at + cnt), inside the wave's range
+#pragma unroll
+    for (uint32_t j = 0; j < SCR_L; ++j)
+        for (uint32_t x = 0; x < len[j]; ++x) {
+            const uint64_t own = g.owners[beg[j] + x];
+            const uint32_t q = (uint32_t)(own >> 32) & 0x7FFFFFFFu;
+            const uint64_t m = g.qoff[q + 1] - g.qoff[q], i = own & 0xFFFFFFFFull;
+            const uint32_t o = (((is_fwd >> j) & 1u) != (uint32_t)(own >> 63)) ? 1u : 0u;
+            const uint64_t io = o ? m - k - i : i, e = p0 + j + (m - k) - io;   // (m - k - io >= 0)
+            g.buf[at++] = ((((uint64_t)q << g.rec_bits | rec) << 1 | o) << g.band_bits) | (e >> HIT_BAND_SHIFT);
+        }
 }
 
 // ---- Layer B: vote --------------------------------------------------------------------------------------------------------------
@@ -678,7 +839,10 @@ namespace {
 // align: the traceback of every chunk's winners (align.hip) right behind their distances, while the chunk's windows exist.
 // min_seeds > 0: the loci mode (it implies align) -- behind the winners of a chunk, every locus of the chunk's runs is listed,
 // measured and traced the same way; after the last chunk the lists are ordered and reduced per cell (finish_loci)
-void batch_best_hits(const sw_batch &b, const uint64_t *offsets, const char *blob, uint64_t nq, uint32_t k, bool align, uint64_t min_seeds, sw_hits &o)
+// seed_copies: 0 -- the unique-seed route (seed_q / seed_i / seed_fc, k_hit_probe); 1 .. 256 -- the cap of the shared-seed route (owner
+// lists, k_hit_probe_shared).  Everything behind the probe is the same code for both
+void batch_best_hits(const sw_batch &b, const uint64_t *offsets, const char *blob, uint64_t nq, uint32_t k, bool align, uint64_t min_seeds, uint32_t seed_copies,
+                     sw_hits &o)
 {
     const bool loci = min_seeds > 0;
     std::vector<LociChunk> loci_chunks;
@@ -717,23 +881,60 @@ void batch_best_hits(const sw_batch &b, const uint64_t *offsets, const char *blo
     QuerySide Q;
     build_query_side(offsets, blob, nq, k, stream, Q);
     QueryPack P;
-    DevArray<uint32_t> seed_q, seed_i;
+    DevArray<uint32_t> seed_q, seed_i, occ_off;
     DevArray<uint8_t> seed_fc;
+    DevArray<uint64_t> owners;
     uint64_t n_seeds_total = 0;
+    unsigned long long seed_stat[SS_N] = {};
+    const bool shared = seed_copies > 0;
+    if (shared && nq > (1ull << 31))
+        raise(SW_ERR_VALUE, "best hits: %llu queries exceed the 31 bits an owner record of the shared seeds has for a query", (unsigned long long)nq);
     if (Q.n_distinct) {
         DevArray<uint32_t> mult(Q.n_distinct), d_ns(nq);
-        seed_q.alloc(Q.n_distinct);
-        seed_i.alloc(Q.n_distinct);
-        seed_fc.alloc(Q.n_distinct);
+        DevArray<unsigned long long> d_stat(SS_N);
         SW_HIP(hipMemsetAsync(mult.p, 0, Q.n_distinct * 4, stream));
         SW_HIP(hipMemsetAsync(d_ns.p, 0, nq * 4, stream));
-        SW_HIP(hipMemsetAsync(seed_q.p, 0xFF, Q.n_distinct * 4, stream));
-        SW_HIP(hipMemsetAsync(seed_i.p, 0, Q.n_distinct * 4, stream));
-        SW_HIP(hipMemsetAsync(seed_fc.p, 0, Q.n_distinct, stream));
+        SW_HIP(hipMemsetAsync(d_stat.p, 0, sizeof seed_stat, stream));
         launch_1d(k_hit_mult, Q.n_valid, stream, (const uint32_t *)Q.sidx.p, (const uint32_t *)Q.number.p, mult.p);
-        launch_1d(k_hit_seeds, Q.n_valid, stream, (const uint32_t *)Q.sidx.p, (const uint32_t *)Q.number.p, (const uint32_t *)mult.p, (const uint64_t *)Q.by_number.p,
-                  (const uint32_t *)Q.vpos.p, (const uint8_t *)Q.text.p, (const uint64_t *)Q.d_off.p, (uint32_t)nq, k, seed_q.p, seed_i.p, seed_fc.p, d_ns.p);
+        if (!shared) {
+            seed_q.alloc(Q.n_distinct);
+            seed_i.alloc(Q.n_distinct);
+            seed_fc.alloc(Q.n_distinct);
+            SW_HIP(hipMemsetAsync(seed_q.p, 0xFF, Q.n_distinct * 4, stream));
+            SW_HIP(hipMemsetAsync(seed_i.p, 0, Q.n_distinct * 4, stream));
+            SW_HIP(hipMemsetAsync(seed_fc.p, 0, Q.n_distinct, stream));
+            launch_1d(k_hit_seeds, Q.n_valid, stream, (const uint32_t *)Q.sidx.p, (const uint32_t *)Q.number.p, (const uint32_t *)mult.p, (const uint64_t *)Q.by_number.p,
+                      (const uint32_t *)Q.vpos.p, (const uint8_t *)Q.text.p, (const uint64_t *)Q.d_off.p, (uint32_t)nq, k, seed_q.p, seed_i.p, seed_fc.p, d_ns.p);
+            launch_1d(k_hit_keep, Q.n_distinct, stream, (const uint32_t *)mult.p, (const uint64_t *)Q.by_number.p, k, 1u, (uint32_t *)nullptr, d_stat.p);
+        } else {
+            // owner lists as CSR over the distinct words: the kept counts, their scan, the windows sorted by (word, window), the fill
+            DevArray<uint32_t> kept(Q.n_distinct);
+            occ_off.alloc(Q.n_distinct + 1);
+            launch_1d(k_hit_keep, Q.n_distinct, stream, (const uint32_t *)mult.p, (const uint64_t *)Q.by_number.p, k, seed_copies, kept.p, d_stat.p);
+            {
+                size_t tmp_bytes = 0;
+                auto in = rocprim::make_transform_iterator(rocprim::make_counting_iterator<uint64_t>(0), KeptAt{kept.p, Q.n_distinct});
+                SW_HIP(rocprim::exclusive_scan(nullptr, tmp_bytes, in, occ_off.p, uint32_t(0), Q.n_distinct + 1, rocprim::plus<uint32_t>(), stream));
+                DevArray<unsigned char> tmp(tmp_bytes);
+                SW_HIP(rocprim::exclusive_scan(tmp.p, tmp_bytes, in, occ_off.p, uint32_t(0), Q.n_distinct + 1, rocprim::plus<uint32_t>(), stream));
+                SW_HIP(hipStreamSynchronize(stream));
+            }
+            uint32_t n_owners = 0;   // (<= the valid windows < 2^32)
+            SW_HIP(hipMemcpyAsync(&n_owners, occ_off.p + Q.n_distinct, 4, hipMemcpyDeviceToHost, stream));
+            SW_HIP(hipStreamSynchronize(stream));
+            owners.alloc(n_owners);
+            if (n_owners) {
+                DevArray<uint64_t> ok_a(Q.n_valid), ok_b(Q.n_valid);
+                launch_1d(k_own_keys, Q.n_valid, stream, (const uint32_t *)Q.sidx.p, (const uint32_t *)Q.number.p, ok_a.p);
+                uint64_t *kp = ok_a.p, *ap = ok_b.p;
+                sort_all_bits(kp, ap, Q.n_valid, stream);
+                launch_1d(k_own_fill, Q.n_valid, stream, (const uint64_t *)kp, (const uint32_t *)kept.p, (const uint32_t *)occ_off.p, (const uint64_t *)Q.by_number.p,
+                          (const uint32_t *)Q.vpos.p, (const uint8_t *)Q.text.p, (const uint64_t *)Q.d_off.p, (uint32_t)nq, k, owners.p, d_ns.p);
+                SW_HIP(hipStreamSynchronize(stream));   // (the sort's buffers are read until here)
+            }
+        }
         SW_HIP(hipMemcpyAsync(o.n_seeds.data(), d_ns.p, nq * 4, hipMemcpyDeviceToHost, stream));
+        SW_HIP(hipMemcpyAsync(seed_stat, d_stat.p, sizeof seed_stat, hipMemcpyDeviceToHost, stream));
         SW_HIP(hipStreamSynchronize(stream));
         for (uint32_t s : o.n_seeds) n_seeds_total += s;
     }
@@ -770,6 +971,15 @@ void batch_best_hits(const sw_batch &b, const uint64_t *offsets, const char *blo
         g.k = k;
         g.band_bits = band_bits;
         g.rec_bits = rec_bits;
+        HitSharedArgs gs{};
+        gs.t = g.t;
+        gs.occ_off = occ_off.p;
+        gs.owners = owners.p;
+        gs.qoff = P.off.p;
+        gs.cursor = d_cursor.p;
+        gs.k = k;
+        gs.band_bits = band_bits;
+        gs.rec_bits = rec_bits;
         const uint32_t blocks_max = launch_blocks("SEQWIN_AMD_HIT_MAX_BLOCKS");   // the probe kernel's; the switch (test library) lowers it
         Event c0, c1, c2, c3;
         uint64_t rows = n_asm;
@@ -781,7 +991,14 @@ void batch_best_hits(const sw_batch &b, const uint64_t *offsets, const char *blo
             g.buf = buf_a.p;
             g.cap = cap_keys;
             g.v = tiles.view(T.asm_tile_off[a0], T.asm_tile_off[a1]);
-            launches += launch_tiles(k_hit_probe, g, blocks_max, stream);
+            if (shared) {
+                gs.buf = buf_a.p;
+                gs.cap = cap_keys;
+                gs.v = g.v;
+                launches += launch_tiles(k_hit_probe_shared, gs, blocks_max, stream);
+            } else {
+                launches += launch_tiles(k_hit_probe, g, blocks_max, stream);
+            }
             unsigned long long n_hits = 0;
             SW_HIP(hipMemcpyAsync(&n_hits, d_cursor.p, 8, hipMemcpyDeviceToHost, stream));
             SW_HIP(hipEventRecord(c1, stream));
@@ -900,6 +1117,9 @@ void batch_best_hits(const sw_batch &b, const uint64_t *offsets, const char *blo
     }
     const uint64_t cn[10] = {hits, n_seeds_total, chunks, splits, launches, aligned, striped, Q.n_distinct, cap_keys, grows};
     memcpy(o.counters, cn, sizeof cn);
+    const uint64_t sc[8] = {seed_copies, seed_stat[SS_WORDS], seed_stat[SS_OCC], seed_stat[SS_DROPPED_WORDS], seed_stat[SS_DROPPED_OCC], seed_stat[SS_PALINDROMES],
+                            seed_stat[SS_LONGEST], hits};
+    memcpy(o.seed_counters, sc, sizeof sc);
 }
 
 }  // namespace
@@ -926,11 +1146,13 @@ void check_infix_pairs(const char *what, const sw_batch *b, const uint64_t *offs
 
 namespace {
 
-// min_seeds: nullptr without the loci mode
+// min_seeds: nullptr without the loci mode; seed_copies: nullptr for the unique-seed route
 void best_hits_entry(const sw_batch *batch, const uint64_t *offsets, const char *blob, uint64_t n_queries, uint64_t k, bool align, const uint64_t *min_seeds,
-                     sw_hits **out)
+                     sw_hits **out, const uint64_t *seed_copies = nullptr)
 {
     if (k < 1 || k > 32) raise(SW_ERR_VALUE, "best hits: k-mer length must lie in 1..32 (got %llu)", (unsigned long long)k);
+    if (seed_copies && (*seed_copies < 1 || *seed_copies > 256))
+        raise(SW_ERR_VALUE, "best hits: seed_copies must lie in 1..256 (got %llu)", (unsigned long long)*seed_copies);
     if (min_seeds && !*min_seeds) raise(SW_ERR_VALUE, "best hits: min_seeds must be at least 1 (got 0)");
     if (!batch || !out) raise(SW_ERR_VALUE, "best hits: a NULL handle or array");
     check_queries("best hits", offsets, blob, n_queries);
@@ -939,7 +1161,7 @@ void best_hits_entry(const sw_batch *batch, const uint64_t *offsets, const char 
     StreamScope scope(HIT_STREAM);
     std::unique_ptr<sw_hits> o(new sw_hits);
     o->device = batch->device;
-    batch_best_hits(*batch, offsets, blob, n_queries, (uint32_t)k, align, min_seeds ? *min_seeds : 0, *o);
+    batch_best_hits(*batch, offsets, blob, n_queries, (uint32_t)k, align, min_seeds ? *min_seeds : 0, seed_copies ? (uint32_t)*seed_copies : 0u, *o);
     *out = o.release();
 }
 
@@ -986,6 +1208,23 @@ int sw_batch_best_hits_aligned(const sw_batch *batch, const uint64_t *offsets, c
 int sw_batch_best_hits_loci(const sw_batch *batch, const uint64_t *offsets, const char *blob, uint64_t n_queries, uint64_t k, uint64_t min_seeds, sw_hits **out)
 {
     return guarded([&] { best_hits_entry(batch, offsets, blob, n_queries, k, true, &min_seeds, out); });
+}
+
+int sw_batch_best_hits_shared(const sw_batch *batch, const uint64_t *offsets, const char *blob, uint64_t n_queries, uint64_t k, uint64_t seed_copies, uint64_t mode,
+                              uint64_t min_seeds, sw_hits **out)
+{
+    return guarded([&] {
+        if (mode > 2) raise(SW_ERR_VALUE, "best hits: mode %llu is none of plain, aligned, loci (0..2)", (unsigned long long)mode);
+        best_hits_entry(batch, offsets, blob, n_queries, k, mode >= 1, mode == 2 ? &min_seeds : nullptr, out, &seed_copies);
+    });
+}
+
+int sw_hits_seed_stats(const sw_hits *h, uint64_t *counters)
+{
+    return guarded([&] {
+        if (!h) raise(SW_ERR_VALUE, "best hits: a NULL handle");
+        if (counters) memcpy(counters, h->seed_counters, sizeof h->seed_counters);
+    });
 }
 
 static const sw_hits &loci_of(const sw_hits *h)

@@ -85,6 +85,7 @@ struct sw_hits {
     std::vector<uint32_t> n_seeds;                 // [nq]
     sw::DevArray<uint32_t> field[5];               // [nq][n_asm] seeds, record, strand, end, dist
     uint64_t counters[10] = {};
+    uint64_t seed_counters[8] = {};                // sw_hits_seed_stats
     double ms[4] = {};
     std::vector<uint64_t> chunk_hits;
     bool aligned = false;                          // made by sw_batch_best_hits_aligned

@@ -184,7 +184,7 @@ class Batch:
             res += (d,)
         return res
 
-    def best_hits(self, queries, kmerlen: int, align: bool = False, loci: bool = False, min_seeds: int = 1) -> "BestHits":
+    def best_hits(self, queries, kmerlen: int, align: bool = False, loci: bool = False, min_seeds: int = 1, seed_copies=None) -> "BestHits":
         """For every query (a list of ``str`` or ``bytes``) and every assembly: the best seeded locus and the exact infix edit
         distance of the query to the best substring there (csrc/hits.hip).  A seed is a canonical
         ``kmerlen``-mer that exactly one window of ALL the query text has and that is not its own reverse complement: a query whose
@@ -195,12 +195,27 @@ class Batch:
         ``loci=True`` (it implies ``align=True``) also lists EVERY seeded locus of every pair with ``min_seeds`` or more seeds (DESIGN.md
         section 3.2g: a local maximum of the vote over two bands to either side), each measured and traced like a winner: the result
         then answers ``n_loci()``, ``sum_nident()``, ``loci()``, ``loci_intervals()`` and ``loci_stats()``.  The matrix fields do not
-        depend on ``min_seeds``.  ValueError for ``min_seeds < 1``.  Still not BLAST."""
+        depend on ``min_seeds``.  ValueError for ``min_seeds < 1``.  Still not BLAST.
+        ``seed_copies=c`` (1..256, else ValueError) shares seeds between windows of the query text: a
+        canonical k-mer that 1..c windows of ALL the query text have, and that is not its own reverse complement, is a seed owned by
+        every one of those windows, so two alleles in one call, a sequence given twice or a repeat inside a query keep their k-mers;
+        a k-mer with more than c windows is dropped whole (the repeat mask, not truncated to c).  ``n_seeds()[q]`` counts the windows
+        of q that own a seed, a window of the batch with a seed is one hit per owner, and vote, winner, distance, ``align`` and
+        ``loci`` follow from the hits as above.  ``seed_copies=1`` gives the default's results bit for bit; ``None`` (the default) runs
+        the unique-seed route itself.  ``seed_stats()`` says what the cap kept and dropped; the summaries of
+        :mod:`seqwin_amd.markers` (``hit_summary``, ``alignment_summary``, ``repeat_summary``) take such a result unchanged."""
         offs, blob, nq = _query_csr(queries)
         h = c_vp()
+        if loci and int(min_seeds) < 1:
+            raise ValueError(f"min_seeds must be at least 1 (got {min_seeds})")
+        if seed_copies is not None:
+            if not 1 <= int(seed_copies) <= 256:
+                raise ValueError(f"seed_copies must lie in 1..256 (got {seed_copies})")
+            mode = 2 if loci else 1 if align else 0
+            check(lib.sw_batch_best_hits_shared(self._h, _ptr(offs), blob, c_u64(nq), c_u64(int(kmerlen)), c_u64(int(seed_copies)), c_u64(mode),
+                                                c_u64(int(min_seeds) if loci else 0), ctypes.byref(h)))
+            return BestHits(h, aligned=mode >= 1, loci=mode == 2)
         if loci:
-            if int(min_seeds) < 1:
-                raise ValueError(f"min_seeds must be at least 1 (got {min_seeds})")
             check(lib.sw_batch_best_hits_loci(self._h, _ptr(offs), blob, c_u64(nq), c_u64(int(kmerlen)), c_u64(int(min_seeds)), ctypes.byref(h)))
             return BestHits(h, aligned=True, loci=True)
         fn = lib.sw_batch_best_hits_aligned if align else lib.sw_batch_best_hits
@@ -647,12 +662,16 @@ class Markers:
         o = offs.astype(np.int64)
         return batch.screen([blob[o[i]:o[i + 1]] for i in range(len(o) - 1)], kmerlen)
 
-    def best_hits(self, batch: "Batch", kmerlen: int, select=None, align: bool = False, loci: bool = False, min_seeds: int = 1) -> "BestHits":
+    def best_hits(self, batch: "Batch", kmerlen: int, select=None, align: bool = False, loci: bool = False, min_seeds: int = 1,
+                  seed_copies=None) -> "BestHits":
         """:meth:`Batch.best_hits` of the representatives' text -- ``sequences(batch, "reps", select)``, in that order -- against
-        every assembly of ``batch``.  ``kmerlen`` is the caller's choice; it need not be the graph's k."""
+        every assembly of ``batch``.  ``kmerlen`` is the caller's choice; it need not be the graph's k.  ``seed_copies`` is that
+        call's: ``None`` keeps a k-mer as a seed only if one window of all representatives has it, ``c`` in 1..256 lets up to c
+        windows share it (representatives that overlap or repeat keep their k-mers) and drops a k-mer with more windows whole."""
         offs, blob, _ = self.sequences(batch, "reps", select)
         o = offs.astype(np.int64)
-        return batch.best_hits([blob[o[i]:o[i + 1]] for i in range(len(o) - 1)], kmerlen, align=align, loci=loci, min_seeds=min_seeds)
+        return batch.best_hits([blob[o[i]:o[i + 1]] for i in range(len(o) - 1)], kmerlen, align=align, loci=loci, min_seeds=min_seeds,
+                               seed_copies=seed_copies)
 
     def candidates(self, min_len: int) -> np.ndarray:
         """Indices of the subgraphs the reference keeps (markers.py:514-517): len >= min_len, neither single nor dup."""
@@ -1023,6 +1042,16 @@ class BestHits:
         check(lib.sw_hits_chunk_hits(self._h, per))
         d.update(query_ms=ms[0], probe_ms=ms[1], vote_ms=ms[2], distance_ms=ms[3], chunk_hits=[int(x) for x in per][:d["chunks"]])
         return d
+
+    def seed_stats(self) -> dict:
+        """What the seed rule kept and dropped: ``seed_copies`` (0: the default, unique-seed call, whose
+        rule is the one at 1), ``seed_words`` and the ``seed_windows`` that own them, ``dropped_words`` with more windows than the
+        cap and their ``dropped_windows``, ``palindromic_words`` (their own reverse complement: never a seed, not counted as
+        dropped), ``longest_owner_list`` and ``hits`` appended over all chunks."""
+        c = (c_u64 * 8)()
+        check(lib.sw_hits_seed_stats(self._h, c))
+        return dict(zip(("seed_copies", "seed_words", "seed_windows", "dropped_words", "dropped_windows", "palindromic_words", "longest_owner_list",
+                         "hits"), (int(x) for x in c)))
 
     def close(self) -> None:
         if self._h:
