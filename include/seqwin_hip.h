@@ -596,6 +596,45 @@ int sw_batch_best_hits_shared(const sw_batch *batch, const uint64_t *offsets, co
  * mult; they are not counted as dropped), the longest owner list, hits appended over all chunks }. */
 int sw_hits_seed_stats(const sw_hits *h, uint64_t *counters);
 
+/* ---- local alignments with affine gap scores at every pair of Layer A (csrc/local.hip) ---------------------------------------------
+ * By DESIGN.md section 3.2i (tests/tools/local_host.py restates it twice).  It is NOT BLAST: the seeds and the window are ours, the
+ * dynamic programme is exhaustive inside the window (no X-drop), there is no e-value filter, no bit score, and none of
+ * MarkerMetrics is filled.  A pair is Layer A's: pattern P = the query or its reverse complement (m bases), text T = [start, stop)
+ * of the record (n bases); an invalid base equals nothing.  Scoring (reward r in 1..255, penalty p in -255..-1, gapopen go in
+ * 0..255, gapextend ge in 1..255; blastn's defaults are 2, -3, 5, 2): a gap of L columns costs go + L * ge.
+ *   E[i][j] = max(E[i][j-1], H[i][j-1] - go) - ge      F[i][j] = max(F[i-1][j], H[i-1][j] - go) - ge
+ *   H[i][j] = max(0, H[i-1][j-1] + s(i,j), E[i][j], F[i][j]),  borders H = 0, E = F = -infinity
+ * Every value carries the record (i0, j0, mismatch, gapopen, gaps) of one canonical alignment: H = 0 carries (i, j, 0, 0, 0);
+ * extension wins a tie against opening; a positive H takes the first of diagonal, E, F that attains the maximum.  score = max H at
+ * the maximal cell (i*, j*) with the smallest j, then the smallest i; qstart = i0, qend = i* (half-open, in P's orientation),
+ * sstart = start + j0, send = start + j*; ins = (gaps + (i* - i0) - (j* - j0)) / 2, nident = (i* - i0) - mismatch - ins.
+ * score == 0 (an empty side, or no match): every count 0, qstart = qend = 0, sstart = send = start. */
+typedef struct sw_scoring {
+    int32_t reward, penalty, gapopen, gapextend;
+} sw_scoring;
+/* The nine figures of n pairs (host arrays of n; any of them may be NULL).  Checks and errors are sw_batch_infix_distances';
+ * a scoring value outside its range, a NULL scoring, or a pair with m >= 2^16 or n >= 2^16 -> SW_ERR_VALUE, all before a device is
+ * touched.  counters[6] (or NULL) = { pairs, sum of m * n, pairs in more than one stripe, pairs with an HBM carry row, launches, rows
+ * of a group pass }; ms[1] (or NULL): the kernels (HIP events). */
+int sw_batch_local_alignments(const sw_batch *b, const uint64_t *offsets, const char *blob, uint64_t n_queries, const sw_infix_pair *pairs,
+                              uint64_t n, const sw_scoring *scoring, uint32_t *score, uint32_t *qstart, uint32_t *qend, uint32_t *sstart,
+                              uint32_t *send, uint32_t *nident, uint32_t *mismatch, uint32_t *gapopen, uint32_t *gaps, uint64_t *counters,
+                              double *ms);
+/* Best hits with the local alignment of every winner (and, in mode 2, of every locus) on its window.  seed_copies 0: the
+ * unique-seed route, else as sw_batch_best_hits_shared; mode and min_seeds as there.  Everything that mode's call returns is
+ * returned bit for bit; in addition nine [n_queries][n_assemblies] fields (sw_hits_local_block; a cell without a hit holds
+ * 0xFFFFFFFF) and, in mode 2, nine list columns in the loci's order (sw_hits_loci_local).  A query above 65279 bases (its window
+ * would reach 2^16) or a scoring value outside its range -> SW_ERR_VALUE before a device is touched. */
+int sw_batch_best_hits_local(const sw_batch *batch, const uint64_t *offsets, const char *blob, uint64_t n_queries, uint64_t k, uint64_t seed_copies,
+                             uint64_t mode, uint64_t min_seeds, const sw_scoring *scoring, sw_hits **out);
+/* field: 0 score, 1 qstart, 2 qend, 3 sstart, 4 send, 5 nident, 6 mismatch, 7 gapopen, 8 gaps.  These three return SW_ERR_VALUE for
+ * hits made without the local alignment (sw_hits_loci_local also for hits made without the loci). */
+int sw_hits_local_block(const sw_hits *h, uint64_t field, uint64_t r0, uint64_t r1, uint64_t c0, uint64_t c1, uint32_t *out);
+int sw_hits_loci_local(const sw_hits *h, uint32_t *score, uint32_t *qstart, uint32_t *qend, uint32_t *sstart, uint32_t *send, uint32_t *nident,
+                       uint32_t *mismatch, uint32_t *gapopen, uint32_t *gaps);
+/* counters[6] and ms[1] as sw_batch_local_alignments', summed over the chunks, winners and loci together. */
+int sw_hits_local_stats(const sw_hits *h, uint64_t *counters, double *ms);
+
 /* ---- multi-GPU merge (one process per GPU; the exchange itself is done by the host side with
  *      torch.distributed / RCCL on the device buffers below).  Together these replace
  *      merge_thread_graphs (cpp/src/seqwin/build_internals.cpp:295-392) across GPUs. -------------- */

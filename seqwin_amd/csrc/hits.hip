@@ -706,6 +706,21 @@ __global__ __launch_bounds__(SCR_TPB) void k_loci_bounds(uint64_t base, uint64_t
     if (j + 1 == n || query[j + 1] * n_asm + assembly[j + 1] != cell) past[cell] = g0 + j + 1;
 }
 
+// the local alignment's nine columns of a chunk's entries, to the place k_loci_gather gave the entry
+struct LocalPtrs {
+    uint32_t *f[LOCAL_FIELDS];
+};
+__global__ __launch_bounds__(SCR_TPB) void k_loci_gather_local(uint64_t base, uint64_t end, const uint32_t *__restrict__ query, const uint32_t *__restrict__ assembly,
+                                                               LocalPtrs in, uint64_t g0, uint64_t n_asm, const uint64_t *__restrict__ first,
+                                                               const uint64_t *__restrict__ cell_off, LocalPtrs out)
+{
+    const uint64_t j = base + (uint64_t)blockIdx.x * SCR_TPB + threadIdx.x;
+    if (j >= end) return;
+    const uint64_t cell = query[j] * n_asm + assembly[j], dst = cell_off[cell] + (g0 + j - first[cell]);
+#pragma unroll
+    for (uint32_t f = 0; f < LOCAL_FIELDS; ++f) out.f[f][dst] = in.f[f][j];
+}
+
 struct CellCount {
     const uint64_t *first, *past;
     uint64_t n;
@@ -752,6 +767,7 @@ __global__ __launch_bounds__(SCR_TPB) void k_loci_reduce(uint64_t base, uint64_t
 struct LociChunk {
     uint64_t n = 0;
     DevArray<uint32_t> f[LF_CHUNK];
+    DevArray<uint32_t> lf[LOCAL_FIELDS];   // the local alignment's figures (allocated with a scoring system only)
     LociPtrs ptrs() const
     {
         LociPtrs p;
@@ -765,7 +781,7 @@ struct AsU64 {
 };
 
 // the chunks' lists into the final order (query, assembly, record, orientation, band), duplicates, and the per-cell reduction
-void finish_loci(std::vector<LociChunk> &chunks, uint64_t nq, uint64_t n_asm, uint64_t max_q, hipStream_t stream, HitLoci &L)
+void finish_loci(std::vector<LociChunk> &chunks, uint64_t nq, uint64_t n_asm, uint64_t max_q, hipStream_t stream, HitLoci &L, bool local)
 {
     const uint64_t n_cells = nq * n_asm;
     uint64_t total = 0;
@@ -775,6 +791,8 @@ void finish_loci(std::vector<LociChunk> &chunks, uint64_t nq, uint64_t n_asm, ui
     L.n_loci.alloc(n_cells);
     L.sum_nident.alloc(n_cells);
     for (int f = 0; f < LOCI_LIST_FIELDS; ++f) L.f[f].alloc(total);
+    if (local)
+        for (uint32_t f = 0; f < LOCAL_FIELDS; ++f) L.lf[f].alloc(total);
     if (!total) {
         SW_HIP(hipMemsetAsync(L.cell_off.p, 0, (n_cells + 1) * 8, stream));
         if (n_cells) {
@@ -805,6 +823,15 @@ void finish_loci(std::vector<LociChunk> &chunks, uint64_t nq, uint64_t n_asm, ui
     g0 = 0;
     for (LociChunk &c : chunks) {
         launch_1d(k_loci_gather, c.n, stream, c.ptrs(), g0, n_asm, (const uint64_t *)first.p, (const uint64_t *)L.cell_off.p, out);
+        if (local) {
+            LocalPtrs lin, lout;
+            for (uint32_t f = 0; f < LOCAL_FIELDS; ++f) {
+                lin.f[f] = c.lf[f].p;
+                lout.f[f] = L.lf[f].p;
+            }
+            launch_1d(k_loci_gather_local, c.n, stream, (const uint32_t *)c.f[LF_QUERY].p, (const uint32_t *)c.f[LF_ASM].p, lin, g0, n_asm, (const uint64_t *)first.p,
+                      (const uint64_t *)L.cell_off.p, lout);
+        }
         g0 += c.n;
     }
     launch_1d(k_hit_dups, total, stream, out, L.f[LF_DUP].p);
@@ -841,8 +868,10 @@ namespace {
 // measured and traced the same way; after the last chunk the lists are ordered and reduced per cell (finish_loci)
 // seed_copies: 0 -- the unique-seed route (seed_q / seed_i / seed_fc, k_hit_probe); 1 .. 256 -- the cap of the shared-seed route (owner
 // lists, k_hit_probe_shared).  Everything behind the probe is the same code for both
+// local != nullptr: the local alignment (local.hip) of the winners' pairs, and in loci mode of the loci's,
+// right behind their distances; nullptr: not one pass more than before
 void batch_best_hits(const sw_batch &b, const uint64_t *offsets, const char *blob, uint64_t nq, uint32_t k, bool align, uint64_t min_seeds, uint32_t seed_copies,
-                     sw_hits &o)
+                     const sw_scoring *local, sw_hits &o)
 {
     const bool loci = min_seeds > 0;
     std::vector<LociChunk> loci_chunks;
@@ -865,6 +894,12 @@ void batch_best_hits(const sw_batch &b, const uint64_t *offsets, const char *blo
         for (int f = 0; f < 4; ++f) {
             o.afield[f].alloc(n_cells);
             if (n_cells) SW_HIP(hipMemsetAsync(o.afield[f].p, 0xFF, n_cells * 4, stream));
+        }
+    o.has_local = local != nullptr;
+    if (local)
+        for (uint32_t f = 0; f < LOCAL_FIELDS; ++f) {
+            o.lfield[f].alloc(n_cells);
+            if (n_cells) SW_HIP(hipMemsetAsync(o.lfield[f].p, 0xFF, n_cells * 4, stream));
         }
     // the key's fields: query | record | orientation | band, the band field one value wider than the largest band (b + 1 is looked at)
     uint64_t max_q = 0, max_rec = 0;
@@ -1073,6 +1108,11 @@ void batch_best_hits(const sw_batch &b, const uint64_t *offsets, const char *blo
                     uint32_t *const out[4] = {o.afield[0].p, o.afield[1].p, o.afield[2].p, o.afield[3].p};
                     align_device(runs_of(runs.t), P, pairs.p, out_idx.p, n_pairs, o.field[4].p, o.field[3].p, out, nullptr, nullptr, o.align);
                 }
+                if (local) {
+                    uint32_t *lout[LOCAL_FIELDS];
+                    for (uint32_t f = 0; f < LOCAL_FIELDS; ++f) lout[f] = o.lfield[f].p;
+                    local_device(runs_of(runs.t), P, pairs.p, out_idx.p, n_pairs, *local, lout, o.local);
+                }
                 if (loci) {
                     // every locus of the chunk's runs: peaks, their list, then Layer A and the traceback as for the winners
                     Event l0, l1;
@@ -1098,6 +1138,14 @@ void batch_best_hits(const sw_batch &b, const uint64_t *offsets, const char *blo
                     o.loci.aligned += lcn[0];
                     uint32_t *const lout[4] = {lc.f[LF_START].p, lc.f[LF_NIDENT].p, lc.f[LF_MISMATCH].p, lc.f[LF_GAPS].p};
                     align_device(runs_of(runs.t), P, lpairs.p, nullptr, lc.n, lc.f[LF_DIST].p, lc.f[LF_END].p, lout, nullptr, nullptr, o.loci.align);
+                    if (local) {
+                        uint32_t *llout[LOCAL_FIELDS];
+                        for (uint32_t f = 0; f < LOCAL_FIELDS; ++f) {
+                            lc.lf[f].alloc(lc.n);
+                            llout[f] = lc.lf[f].p;
+                        }
+                        local_device(runs_of(runs.t), P, lpairs.p, nullptr, lc.n, *local, llout, o.local);
+                    }
                     if (lc.n) loci_chunks.push_back(std::move(lc));
                 }
             }
@@ -1108,7 +1156,7 @@ void batch_best_hits(const sw_batch &b, const uint64_t *offsets, const char *blo
     if (loci) {
         Event f0, f1;
         SW_HIP(hipEventRecord(f0, stream));
-        finish_loci(loci_chunks, nq, n_asm, max_q, stream, o.loci);
+        finish_loci(loci_chunks, nq, n_asm, max_q, stream, o.loci, local != nullptr);
         SW_HIP(hipEventRecord(f1, stream));
         SW_HIP(hipStreamSynchronize(stream));
         SW_HIP(hipEventElapsedTime(&fms, f0, f1));
@@ -1148,7 +1196,7 @@ namespace {
 
 // min_seeds: nullptr without the loci mode; seed_copies: nullptr for the unique-seed route
 void best_hits_entry(const sw_batch *batch, const uint64_t *offsets, const char *blob, uint64_t n_queries, uint64_t k, bool align, const uint64_t *min_seeds,
-                     sw_hits **out, const uint64_t *seed_copies = nullptr)
+                     sw_hits **out, const uint64_t *seed_copies = nullptr, const sw_scoring *local = nullptr)
 {
     if (k < 1 || k > 32) raise(SW_ERR_VALUE, "best hits: k-mer length must lie in 1..32 (got %llu)", (unsigned long long)k);
     if (seed_copies && (*seed_copies < 1 || *seed_copies > 256))
@@ -1156,12 +1204,17 @@ void best_hits_entry(const sw_batch *batch, const uint64_t *offsets, const char 
     if (min_seeds && !*min_seeds) raise(SW_ERR_VALUE, "best hits: min_seeds must be at least 1 (got 0)");
     if (!batch || !out) raise(SW_ERR_VALUE, "best hits: a NULL handle or array");
     check_queries("best hits", offsets, blob, n_queries);
+    if (local)   // a window has at most |query| + 256 bases, and a side of a local alignment stays below 2^16
+        for (uint64_t q = 0; q < n_queries; ++q)
+            if (offsets[q + 1] - offsets[q] > 65279)
+                raise(SW_ERR_VALUE, "best hits: query %llu has %llu bases, above the 65279 the local alignment takes", (unsigned long long)q,
+                      (unsigned long long)(offsets[q + 1] - offsets[q]));
     if (batch->host.rec_len.size() && !batch->d_packed.p) raise(SW_ERR_VALUE, "best hits: the batch holds no packed bases (it must be resident)");
     require_device(batch->device, "the batch");
     StreamScope scope(HIT_STREAM);
     std::unique_ptr<sw_hits> o(new sw_hits);
     o->device = batch->device;
-    batch_best_hits(*batch, offsets, blob, n_queries, (uint32_t)k, align, min_seeds ? *min_seeds : 0, seed_copies ? (uint32_t)*seed_copies : 0u, *o);
+    batch_best_hits(*batch, offsets, blob, n_queries, (uint32_t)k, align, min_seeds ? *min_seeds : 0, seed_copies ? (uint32_t)*seed_copies : 0u, local, *o);
     *out = o.release();
 }
 
@@ -1216,6 +1269,16 @@ int sw_batch_best_hits_shared(const sw_batch *batch, const uint64_t *offsets, co
     return guarded([&] {
         if (mode > 2) raise(SW_ERR_VALUE, "best hits: mode %llu is none of plain, aligned, loci (0..2)", (unsigned long long)mode);
         best_hits_entry(batch, offsets, blob, n_queries, k, mode >= 1, mode == 2 ? &min_seeds : nullptr, out, &seed_copies);
+    });
+}
+
+int sw_batch_best_hits_local(const sw_batch *batch, const uint64_t *offsets, const char *blob, uint64_t n_queries, uint64_t k, uint64_t seed_copies, uint64_t mode,
+                             uint64_t min_seeds, const sw_scoring *scoring, sw_hits **out)
+{
+    return guarded([&] {
+        if (mode > 2) raise(SW_ERR_VALUE, "best hits: mode %llu is none of plain, aligned, loci (0..2)", (unsigned long long)mode);
+        check_scoring("best hits", scoring);
+        best_hits_entry(batch, offsets, blob, n_queries, k, mode >= 1, mode == 2 ? &min_seeds : nullptr, out, seed_copies ? &seed_copies : nullptr, scoring);
     });
 }
 

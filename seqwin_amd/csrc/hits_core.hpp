@@ -24,6 +24,14 @@ struct AlignStats {
     double ms[2] = {};
 };
 
+// The local alignment (local.hip): score, qstart, qend, sstart, send, nident, mismatch, gapopen, gaps.
+// counters[6] = { pairs, sum of m * n, pairs in more than one stripe, pairs with an HBM carry row, launches, rows of a group pass }
+constexpr uint32_t LOCAL_FIELDS = 9;
+struct LocalStats {
+    uint64_t counters[6] = {};
+    double ms[1] = {};
+};
+
 // Every seeded locus of a call made in loci mode, in the list's final order (query, record, strand, band).
 // counters-to-be: n, n_dup, max_per_cell, aligned; ms[4] = { peaks + compact, distances, traceback, final ordering + reduction }
 constexpr int LOCI_LIST_FIELDS = 13;   // query, assembly, record, strand, band, seeds, dist, end, start, nident, mismatch, gaps, dup
@@ -33,6 +41,7 @@ struct HitLoci {
     DevArray<uint64_t> cell_off;              // [nq * n_asm + 1]
     DevArray<uint32_t> n_loci, sum_nident;    // [nq][n_asm]
     AlignStats align;                         // the loci's traceback (the winners' own stays in sw_hits::align)
+    DevArray<uint32_t> lf[LOCAL_FIELDS];               // [n] each: the local alignment's nine figures (made with a scoring system only)
     double ms[4] = {};
 };
 
@@ -57,6 +66,12 @@ void check_infix_pairs(const char *what, const sw_batch *b, const uint64_t *offs
 // at d_ops[d_ops_end[i]] (exclusive), the slot in front of it holding |query| + dist bytes.  st is added to.
 void align_device(const Runs &t, const QueryPack &P, const sw_infix_pair *d_pairs, const uint32_t *d_out_idx, uint64_t n, const uint32_t *d_dist,
                   const uint32_t *d_end, uint32_t *const out[4], uint8_t *d_ops, const uint64_t *d_ops_end, AlignStats &st);
+
+// local.hip: the nine figures of n valid pairs (device list) under scoring system sc, written at the pair's out index; every side
+// of a pair is below 2^16 (the callers check it on the host).  st is added to.
+void check_scoring(const char *what, const sw_scoring *sc);
+void local_device(const Runs &t, const QueryPack &P, const sw_infix_pair *d_pairs, const uint32_t *d_out_idx, uint64_t n, const sw_scoring &sc,
+                  uint32_t *const out[LOCAL_FIELDS], LocalStats &st);
 
 namespace {
 
@@ -93,4 +108,7 @@ struct sw_hits {
     sw::AlignStats align;
     bool has_loci = false;                         // made by sw_batch_best_hits_loci
     sw::HitLoci loci;
+    bool has_local = false;                        // made by sw_batch_best_hits_local
+    sw::DevArray<uint32_t> lfield[sw::LOCAL_FIELDS];   // [nq][n_asm] the local alignment's nine figures (local only)
+    sw::LocalStats local;
 };

@@ -184,7 +184,28 @@ class Batch:
             res += (d,)
         return res
 
-    def best_hits(self, queries, kmerlen: int, align: bool = False, loci: bool = False, min_seeds: int = 1, seed_copies=None) -> "BestHits":
+    def local_alignments(self, queries, pairs, scoring=(2, -3, 5, 2), stats: bool = False) -> dict:
+        """The optimal LOCAL alignment of every pair of :meth:`infix_distances` under the scoring system ``(reward, penalty, gapopen,
+        gapextend)`` -- a gap of L columns costs ``gapopen + L * gapextend``; the default is blastn's (csrc/local.hip, DESIGN.md section
+        3.2i).  A dict of uint32 arrays: ``score``, ``qstart`` / ``qend`` (half-open, in the pattern's orientation), ``sstart`` /
+        ``send`` (half-open record positions), ``nident``, ``mismatch``, ``gapopen`` and ``gaps``; of equal maxima the one that ends in
+        the smallest column, then the smallest row.  ``score == 0`` (an empty side, no match): every count 0 and ``sstart == send ==
+        start``.  Not BLAST: the window is the caller's, the dynamic programme is exhaustive inside it (no X-drop), no e-values, no
+        bit scores.  ValueError for a scoring value outside 1..255, -255..-1, 0..255, 1..255, for a side of 2^16 bases or more, and
+        for what :meth:`infix_distances` refuses.  ``stats=True`` adds the call's counters under ``"stats"``."""
+        offs, blob, nq = _query_csr(queries)
+        pr = _infix_pairs(pairs)
+        out = [np.empty(len(pr), np.uint32) for _ in LOCAL_FIELDS]
+        c = (c_u64 * 6)()
+        ms = (ctypes.c_double * 1)()
+        check(lib.sw_batch_local_alignments(self._h, _ptr(offs), blob, c_u64(nq), _ptr(pr), c_u64(len(pr)), _scoring(scoring), *[_ptr(a) for a in out], c, ms))
+        res = dict(zip(LOCAL_FIELDS, out))
+        if stats:
+            res["stats"] = dict(zip(_LOCAL_COUNTERS, (int(x) for x in c)), local_ms=ms[0])
+        return res
+
+    def best_hits(self, queries, kmerlen: int, align: bool = False, loci: bool = False, min_seeds: int = 1, seed_copies=None, local: bool = False,
+                  scoring=(2, -3, 5, 2)) -> "BestHits":
         """For every query (a list of ``str`` or ``bytes``) and every assembly: the best seeded locus and the exact infix edit
         distance of the query to the best substring there (csrc/hits.hip).  A seed is a canonical
         ``kmerlen``-mer that exactly one window of ALL the query text has and that is not its own reverse complement: a query whose
@@ -203,11 +224,24 @@ class Batch:
         of q that own a seed, a window of the batch with a seed is one hit per owner, and vote, winner, distance, ``align`` and
         ``loci`` follow from the hits as above.  ``seed_copies=1`` gives the default's results bit for bit; ``None`` (the default) runs
         the unique-seed route itself.  ``seed_stats()`` says what the cap kept and dropped; the summaries of
-        :mod:`seqwin_amd.markers` (``hit_summary``, ``alignment_summary``, ``repeat_summary``) take such a result unchanged."""
+        :mod:`seqwin_amd.markers` (``hit_summary``, ``alignment_summary``, ``repeat_summary``) take such a result unchanged.
+        ``local=True`` (it combines with everything above and changes none of it) adds the optimal local
+        alignment of every winner on its window under ``scoring`` (:meth:`local_alignments`): the result then answers ``score()``,
+        ``qstart()``, ``qend()``, ``sstart()``, ``send()``, ``local_nident()``, ``local_mismatch()``, ``local_gapopen()``,
+        ``local_gaps()`` and ``local_stats()``, and with ``loci=True`` its ``loci()`` has nine ``local_*`` columns.  A copy of which
+        an assembly holds only a part reads as a large ``dist`` and as a clean local hit over that part.  Still not BLAST: our seeds and
+        windows, no X-drop, no e-values.  ValueError for a query above 65279 bases."""
         offs, blob, nq = _query_csr(queries)
         h = c_vp()
         if loci and int(min_seeds) < 1:
             raise ValueError(f"min_seeds must be at least 1 (got {min_seeds})")
+        if local:
+            if seed_copies is not None and not 1 <= int(seed_copies) <= 256:
+                raise ValueError(f"seed_copies must lie in 1..256 (got {seed_copies})")
+            mode = 2 if loci else 1 if align else 0
+            check(lib.sw_batch_best_hits_local(self._h, _ptr(offs), blob, c_u64(nq), c_u64(int(kmerlen)), c_u64(int(seed_copies or 0)), c_u64(mode),
+                                               c_u64(int(min_seeds) if loci else 0), _scoring(scoring), ctypes.byref(h)))
+            return BestHits(h, aligned=mode >= 1, loci=mode == 2, local=True)
         if seed_copies is not None:
             if not 1 <= int(seed_copies) <= 256:
                 raise ValueError(f"seed_copies must lie in 1..256 (got {seed_copies})")
@@ -272,6 +306,18 @@ def _query_csr(queries):
     offs = np.zeros(len(qs) + 1, np.uint64)
     np.cumsum([len(q) for q in qs], out=offs[1:])
     return offs, b"".join(qs), len(qs)
+
+
+LOCAL_FIELDS = ("score", "qstart", "qend", "sstart", "send", "nident", "mismatch", "gapopen", "gaps")
+_LOCAL_COUNTERS = ("pairs", "cells", "striped_pairs", "hbm_carry_pairs", "launches", "pass_rows")
+
+
+def _scoring(scoring):
+    """``(reward, penalty, gapopen, gapextend)`` as the int32[4] a ``sw_scoring`` is; the library checks the ranges."""
+    v = [int(x) for x in scoring]
+    if len(v) != 4 or any(abs(x) >= 1 << 31 for x in v):
+        raise ValueError(f"scoring must be (reward, penalty, gapopen, gapextend) (got {scoring!r})")
+    return (ctypes.c_int32 * 4)(*v)
 
 
 def _infix_pairs(pairs) -> np.ndarray:
@@ -663,15 +709,16 @@ class Markers:
         return batch.screen([blob[o[i]:o[i + 1]] for i in range(len(o) - 1)], kmerlen)
 
     def best_hits(self, batch: "Batch", kmerlen: int, select=None, align: bool = False, loci: bool = False, min_seeds: int = 1,
-                  seed_copies=None) -> "BestHits":
+                  seed_copies=None, local: bool = False, scoring=(2, -3, 5, 2)) -> "BestHits":
         """:meth:`Batch.best_hits` of the representatives' text -- ``sequences(batch, "reps", select)``, in that order -- against
         every assembly of ``batch``.  ``kmerlen`` is the caller's choice; it need not be the graph's k.  ``seed_copies`` is that
         call's: ``None`` keeps a k-mer as a seed only if one window of all representatives has it, ``c`` in 1..256 lets up to c
-        windows share it (representatives that overlap or repeat keep their k-mers) and drops a k-mer with more windows whole."""
+        windows share it (representatives that overlap or repeat keep their k-mers) and drops a k-mer with more windows whole.
+        ``local`` and ``scoring`` are that call's too: the local alignment of every winner (and locus) with affine gap scores."""
         offs, blob, _ = self.sequences(batch, "reps", select)
         o = offs.astype(np.int64)
         return batch.best_hits([blob[o[i]:o[i + 1]] for i in range(len(o) - 1)], kmerlen, align=align, loci=loci, min_seeds=min_seeds,
-                               seed_copies=seed_copies)
+                               seed_copies=seed_copies, local=local, scoring=scoring)
 
     def candidates(self, min_len: int) -> np.ndarray:
         """Indices of the subgraphs the reference keeps (markers.py:514-517): len >= min_len, neither single nor dup."""
@@ -893,12 +940,16 @@ class BestHits:
     ``(lo, hi)`` pair, a slice or a range.  Made with ``align=True`` it also holds the canonical alignment of every hit (csrc/align.hip,
     DESIGN.md section 3.2f): ``start``, ``nident``, ``mismatch`` and ``gaps``, NO_HIT where there is no hit.  Made with ``loci=True`` it
     also holds every seeded locus of every pair: the list ``loci()`` and, per pair, ``n_loci`` and
-    ``sum_nident`` over the loci that are no duplicates -- counts, 0 where there is none."""
+    ``sum_nident`` over the loci that are no duplicates -- counts, 0 where there is none.  Made with ``local=True`` it also holds the
+    optimal local alignment of every hit on its window under an affine scoring system (csrc/local.hip; still
+    not BLAST): ``score``, ``qstart``, ``qend``, ``sstart``, ``send``, ``local_nident``, ``local_mismatch``, ``local_gapopen`` and
+    ``local_gaps``, NO_HIT where there is no hit."""
 
-    def __init__(self, handle: c_vp, aligned: bool = False, loci: bool = False):
+    def __init__(self, handle: c_vp, aligned: bool = False, loci: bool = False, local: bool = False):
         self._h = handle
         self._aligned = aligned
         self._loci = loci
+        self._local = local
 
     def sizes(self):
         """(queries, assemblies, seeds of all queries, k)"""
@@ -980,6 +1031,56 @@ class BestHits:
         d.update(store_ms=ms[0], walk_ms=ms[1])
         return d
 
+    def _local_block(self, field: int, rows, cols) -> np.ndarray:
+        if not self._local:
+            raise ValueError("these best hits were made without local=True")
+        nq, na, _, _ = self.sizes()
+        (r0, r1), (c0, c1) = _block_range(rows, nq), _block_range(cols, na)
+        out = np.empty((max(r1 - r0, 0), max(c1 - c0, 0)), np.uint32)
+        check(lib.sw_hits_local_block(self._h, c_u64(field), c_u64(r0), c_u64(r1), c_u64(c0), c_u64(c1), _ptr(out)))
+        return out
+
+    def score(self, rows=None, cols=None) -> np.ndarray:
+        """uint32[rows, cols]: the raw score of the winner's optimal local alignment on its window (0: nothing matches)."""
+        return self._local_block(0, rows, cols)
+
+    def qstart(self, rows=None, cols=None) -> np.ndarray:
+        """uint32[rows, cols]: the local alignment covers ``[qstart, qend)`` of the query, in the hit's orientation."""
+        return self._local_block(1, rows, cols)
+
+    def qend(self, rows=None, cols=None) -> np.ndarray:
+        return self._local_block(2, rows, cols)
+
+    def sstart(self, rows=None, cols=None) -> np.ndarray:
+        """uint32[rows, cols]: the local alignment covers ``[sstart, send)`` of the hit's record."""
+        return self._local_block(3, rows, cols)
+
+    def send(self, rows=None, cols=None) -> np.ndarray:
+        return self._local_block(4, rows, cols)
+
+    def local_nident(self, rows=None, cols=None) -> np.ndarray:
+        return self._local_block(5, rows, cols)
+
+    def local_mismatch(self, rows=None, cols=None) -> np.ndarray:
+        return self._local_block(6, rows, cols)
+
+    def local_gapopen(self, rows=None, cols=None) -> np.ndarray:
+        return self._local_block(7, rows, cols)
+
+    def local_gaps(self, rows=None, cols=None) -> np.ndarray:
+        """uint32[rows, cols]: gap columns of either side of the local alignment."""
+        return self._local_block(8, rows, cols)
+
+    def local_stats(self) -> dict:
+        """The local stage's counters, winners and loci together: ``pairs``, ``cells`` (sum of m * n), ``striped_pairs`` (more than
+        one pass over the text), ``hbm_carry_pairs``, ``launches``, ``pass_rows`` and ``local_ms``."""
+        if not self._local:
+            raise ValueError("these best hits were made without local=True")
+        c = (c_u64 * 6)()
+        ms = (ctypes.c_double * 1)()
+        check(lib.sw_hits_local_stats(self._h, c, ms))
+        return dict(zip(_LOCAL_COUNTERS, (int(x) for x in c)), local_ms=ms[0])
+
     def _loci_block(self, field: int, rows, cols) -> np.ndarray:
         if not self._loci:
             raise ValueError("these best hits were made without loci=True")
@@ -1000,7 +1101,9 @@ class BestHits:
     def loci(self) -> dict:
         """The list of all loci, ascending by (query, record, strand, band), as parallel arrays: ``query``, ``assembly``, ``record``,
         ``strand``, ``band``, ``seeds``, ``dist``, ``end``, ``start``, ``nident``, ``mismatch``, ``gaps`` and ``dup`` (1: the locus
-        before it is the same copy); ``cell_offsets`` (uint64[queries * assemblies + 1]) bounds the loci of every pair."""
+        before it is the same copy); ``cell_offsets`` (uint64[queries * assemblies + 1]) bounds the loci of every pair.  Made with
+        ``local=True`` too: also ``local_score``, ``local_qstart``, ``local_qend``, ``local_sstart``, ``local_send``, ``local_nident``,
+        ``local_mismatch``, ``local_gapopen`` and ``local_gaps`` of every locus."""
         if not self._loci:
             raise ValueError("these best hits were made without loci=True")
         nq, na, _, _ = self.sizes()
@@ -1011,6 +1114,10 @@ class BestHits:
         check(lib.sw_hits_loci(self._h, _ptr(offs), *[_ptr(a) if n.value else None for a in cols]))
         out = {f: (a.astype(np.uint8) if f in ("strand", "dup") else a) for f, a in zip(LOCI_FIELDS, cols)}
         out["cell_offsets"] = offs
+        if self._local:   # the local alignment of every locus on its window, in the list's order
+            lc = [np.empty(n.value, np.uint32) for _ in LOCAL_FIELDS]
+            check(lib.sw_hits_loci_local(self._h, *[_ptr(a) if n.value else None for a in lc]))
+            out.update({"local_" + f: a for f, a in zip(LOCAL_FIELDS, lc)})
         return out
 
     def loci_intervals(self) -> np.ndarray:

@@ -310,6 +310,72 @@ def repeat_summary(h, lengths, n_tar: int) -> np.ndarray:
     return out
 
 
+LOCAL_SUMMARY_DTYPE = np.dtype([("coverage_tar", "<f8"), ("identity_local_tar", "<f8"), ("f_tar", "<f8"), ("distance_local_neg", "<f8"),
+                                ("f_neg", "<f8")])
+
+
+def _best_locus_cells(h, shape):
+    """Per cell the figures (qstart, qend, nident, mismatch, gaps, hit) of its non-duplicate locus with the highest local score, ties
+    going to the first in list order; computed on the host from ``cell_offsets``."""
+    L = h.loci()
+    offs = L["cell_offsets"].astype(np.int64)
+    keep = np.flatnonzero(L["dup"] == 0)
+    cell = np.searchsorted(offs, keep, side="right") - 1                       # the cell of every kept locus (ascending)
+    order = np.lexsort((keep, -L["local_score"][keep].astype(np.int64), cell))  # by cell, score descending, list order
+    first = order[np.concatenate(([True], cell[order][1:] != cell[order][:-1]))] if len(order) else order
+    out = {f: np.zeros(shape, np.float64).reshape(-1) for f in ("qstart", "qend", "nident", "mismatch", "gaps")}
+    hit = np.zeros(shape, bool).reshape(-1)
+    hit[cell[first]] = True
+    for f in out:
+        out[f][cell[first]] = L["local_" + f][keep[first]]
+    return {f: a.reshape(shape) for f, a in out.items()}, hit.reshape(shape)
+
+
+def local_summary(h, lengths, n_tar: int, best_locus: bool = False) -> np.ndarray:
+    """Per query of a :class:`BestHits` made with ``local=True``, with ``lengths`` the queries' lengths, the targets the first
+    ``n_tar`` columns and the non-targets the rest: ``coverage_tar`` = the mean over ALL targets of ``(qend - qstart) / len`` with 0
+    where there is no hit, ``identity_local_tar`` = the sum of the local ``nident`` over the targets' hits / len / n_tar,
+    ``distance_local_neg`` = the sum of the local ``mismatch + gaps`` over the non-targets' hits / len / n_neg, ``f_tar`` / ``f_neg`` =
+    the share of the group's assemblies with a hit, all in float64.  A query of length 0, and an empty group, read ``nan``.
+    ``best_locus=True`` (hits made with ``loci=True`` too): a cell's figures are those of its non-duplicate locus with the highest
+    local score, ties going to the first in list order, not those of the vote's winner.  A copy of which a non-target holds half
+    reads here as half the coverage at distance 0, where ``alignment_summary`` reads half a query of edits.  The names are
+    deliberately not those of ``MarkerMetrics``: the window is a seeded one, there is no X-drop and no e-value, this is not BLAST,
+    and nothing of it is written into ``signatures.csv``."""
+    lengths = np.asarray(lengths, np.int64).reshape(-1)
+    if best_locus:
+        nq, na = h.sizes()[:2]
+        cells, hit = _best_locus_cells(h, (nq, na))
+        span, nident, edits = cells["qend"] - cells["qstart"], cells["nident"], cells["mismatch"] + cells["gaps"]
+    else:
+        score = np.asarray(h.score(), np.uint32)
+        hit = score != np.uint32(0xFFFFFFFF)
+        f64 = lambda a: np.where(hit, np.asarray(a, np.uint32).astype(np.float64), 0.0)   # noqa: E731
+        span, nident, edits = f64(h.qend()) - f64(h.qstart()), f64(h.local_nident()), f64(h.local_mismatch()) + f64(h.local_gaps())
+    if hit.ndim != 2 or lengths.shape != (hit.shape[0],) or (lengths < 0).any():
+        raise ValueError(f"hits of shape {hit.shape} against {lengths.shape} query lengths")
+    n_tar = int(n_tar)
+    if not 0 <= n_tar <= hit.shape[1]:
+        raise ValueError(f"n_tar = {n_tar} lies outside the {hit.shape[1]} assemblies")
+    out = np.zeros(len(lengths), LOCAL_SUMMARY_DTYPE)
+    ln = lengths.astype(np.float64)
+    ln[ln == 0] = np.nan
+    tar, neg = slice(0, n_tar), slice(n_tar, None)
+    n_neg = hit.shape[1] - n_tar
+    if n_tar:
+        out["coverage_tar"] = span[:, tar].sum(axis=1) / ln / n_tar
+        out["identity_local_tar"] = nident[:, tar].sum(axis=1) / ln / n_tar
+        out["f_tar"] = np.where(np.isnan(ln), np.nan, hit[:, tar].sum(axis=1) / n_tar)
+    else:
+        out["coverage_tar"] = out["identity_local_tar"] = out["f_tar"] = np.nan
+    if n_neg:
+        out["distance_local_neg"] = edits[:, neg].sum(axis=1) / ln / n_neg
+        out["f_neg"] = np.where(np.isnan(ln), np.nan, hit[:, neg].sum(axis=1) / n_neg)
+    else:
+        out["distance_local_neg"] = out["f_neg"] = np.nan
+    return out
+
+
 def cigar(offsets, ops) -> list:
     """The edit scripts of :meth:`Batch.infix_alignments` (``ops=True``) as run-length strings such as ``12=1X3=2I``: ``=`` match,
     ``X`` mismatch, ``I`` a query base facing a gap, ``D`` a text base facing a gap; an empty script is the empty string."""
