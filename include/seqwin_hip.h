@@ -635,6 +635,42 @@ int sw_hits_loci_local(const sw_hits *h, uint32_t *score, uint32_t *qstart, uint
 /* counters[6] and ms[1] as sw_batch_local_alignments', summed over the chunks, winners and loci together. */
 int sw_hits_local_stats(const sw_hits *h, uint64_t *counters, double *ms);
 
+/* ---- oligo search: every place where a primer or probe binds with at most d mismatches, on either strand (csrc/oligo.hip) ----
+ * None of this has a counterpart in the reference.  It is NOT BLAST and NOT a thermodynamic model: no Tm, no dG, no e-values; one
+ * exactly specified quantity, Hamming distance under IUPAC sets, over EVERY window of the resident batch -- no seed is needed, so no
+ * site is missed.  DESIGN.md section 3.2j is the specification, tests/tools/oligo_host.py restates it.
+ * An oligo is 8..32 letters in either case: A C G T, U (= T) or an IUPAC code R Y S W K M B D H V N; every position is a set of
+ * bases.  P0 is the oligo, P1 its reverse complement (the sets complemented, the order reversed).  A site (oligo, strand s, record,
+ * pos) is a window [pos, pos + L) inside one valid run of the record; mm = the number of i with text[pos + i] not in Ps[i].  A hit is
+ * a site with mm <= max_mismatch and no mismatch among the three_prime bases at the oligo's 3' end (strand 0: positions L - c ..
+ * L - 1 of the window, strand 1: positions 0 .. c - 1).  An oligo that equals its reverse complement hits twice at one place. */
+typedef struct sw_oligos sw_oligos; /* opaque: the device-resident [n_oligos][n_assemblies] results of one call, and the site list */
+/* (no counterpart in the reference)  Oligos as the queries of sw_batch_screen (CSR over `blob`).  1..4096 oligos of 8..32 IUPAC
+ * letters, max_mismatch in 0..8 and below the shortest oligo, three_prime in 0..8: anything else -> SW_ERR_VALUE before a device is
+ * touched.  want_sites != 0 also keeps the list of all hits.  A batch of 2^43 bases or more, or a list of 2^32 entries or more ->
+ * SW_ERR_RUNTIME.  A single-device call on a resident batch; returns with the results finished. */
+int sw_batch_oligo_hits(const sw_batch *batch, const uint64_t *offsets, const char *blob, uint64_t n_oligos, uint64_t max_mismatch,
+                        uint64_t three_prime, int want_sites, void *stream, sw_oligos **out);
+/* (no counterpart in the reference)  Oligos, assemblies, max_mismatch, three_prime of the call (any pointer may be NULL). */
+int sw_oligos_sizes(const sw_oligos *h, uint64_t *n_oligos, uint64_t *n_assemblies, uint64_t *max_mismatch, uint64_t *three_prime);
+/* (no counterpart in the reference)  sw_screen_counts for one field: 0 n_sites (hits on both strands), and of the hit that is least
+ * in the order (mm, record, pos, strand): 1 best_mm, 2 best_record (global), 3 best_pos, 4 best_strand -- 0xFFFFFFFF without a hit. */
+int sw_oligos_block(const sw_oligos *h, uint64_t field, uint64_t r0, uint64_t r1, uint64_t c0, uint64_t c1, uint32_t *out);
+/* (no counterpart in the reference)  Entries of the site list.  This and sw_oligos_sites: SW_ERR_VALUE for a result made without it. */
+int sw_oligos_sites_size(const sw_oligos *h, uint64_t *n_sites_total);
+/* (no counterpart in the reference)  Every hit, ascending by (oligo, assembly, record, pos, strand): cell_offsets[n_oligos *
+ * n_assemblies + 1] -- the hits of pair (q, a) are the entries [cell_offsets[q * n_assemblies + a], cell_offsets[q * n_assemblies +
+ * a + 1]) -- and the list's columns, n_sites_total entries each (record is global, strand 0 or 1). */
+int sw_oligos_sites(const sw_oligos *h, uint64_t *cell_offsets, uint32_t *oligo, uint32_t *assembly, uint32_t *record, uint32_t *pos,
+                    uint32_t *strand, uint32_t *mm);
+/* (no counterpart in the reference)  counters[8] = { windows scanned (window ends of the runs of shortest-oligo length or more, summed
+ * over the passes), passes over the batch (groups of oligos), chunks of assemblies, launches of the scan kernel, hits, doublings of
+ * the site buffer, chunks redone in halves, window x pattern comparisons (a pattern = an oligo on a strand) }; ms[2] = { scan, order
+ * of the site list } (HIP events). */
+int sw_oligos_stats(const sw_oligos *h, uint64_t *counters, double *ms);
+/* (no counterpart in the reference) */
+void sw_oligos_free(sw_oligos *h);
+
 /* ---- multi-GPU merge (one process per GPU; the exchange itself is done by the host side with
  *      torch.distributed / RCCL on the device buffers below).  Together these replace
  *      merge_thread_graphs (cpp/src/seqwin/build_internals.cpp:295-392) across GPUs. -------------- */

@@ -1,0 +1,504 @@
+// oligo.hip -- every place in every assembly of a resident batch where a short oligo (a primer, a probe) binds with at most d
+// mismatches, on either strand: Hamming distance under IUPAC sets, exhaustive -- every window of the batch against every oligo.
+//
+// It has no counterpart in the reference, it is NOT BLAST and NOT a thermodynamic model (no Tm, no dG, no e-values), and it fills
+// none of MarkerMetrics.  DESIGN.md section 3.2j is the specification; tests/tools/oligo_host.py restates it twice.
+//
+//   host           an oligo of L = 8..32 letters is L sets of bases.  Per oligo and strand one row of the pattern table (8 words):
+//                  four MISMATCH planes -- bit t of plane b is set iff base b is NOT in the set that faces the text base t places
+//                  before the window's END, for t < L; the length mask is folded into them --, the 3'-clamp mask and L.  Strand 1
+//                  is the reverse complement: its set at t is the complement of the oligo's set at position t.
+//   k_ol_scan      the hot path.  ONE walk for all lengths, windows indexed by their end: the runs of Lmin bases or more (Lmin = the
+//                  shortest oligo of the call) cut into kmer_walk.hpp's tiles, a wave per tile, 16 consecutive window ends per lane.
+//                  A lane keeps the last 32 bases as two 32-bit planes (the low and the high bit of every base; bit 0 = the end) and
+//                  pre-rolls up to 31 bases before its first end, bounded by the run's start.  Per pattern (a wave-uniform loop; the
+//                  table row arrives by scalar loads) and window: a bitwise select of the four planes by the text's two gives the
+//                  mismatch bits in three operations, then popcount, the clamp, the comparison.  Candidates are rare; a wave that
+//                  has one (a ballot) checks it against the run's start -- an oligo of L bases that ends at offset e of its run is
+//                  a site iff e + 1 >= L --, counts it (atomicAdd), offers it as the best site (64-bit atomicMin) and appends it to
+//                  the site buffer (wave_append).  All three are order-independent.
+//   k_ol_resolve   the best site's key -> mm, record, pos, strand of a cell
+//   k_ol_decode    a sorted site key -> assembly, record, pos
+// Oligos are taken in groups (a pass over the batch each), assemblies in chunks bounded by the site buffer: a chunk that overflows
+// is redone in two halves, one assembly that overflows has the buffer doubled -- as hits.hip treats its key buffer.
+#include "screen_core.hpp"
+
+namespace sw {
+namespace {
+
+constexpr uint32_t OL_MIN_LEN = 8, OL_MAX_LEN = 32, OL_MAX_OLIGOS = 4096, OL_MAX_MM = 8, OL_MAX_CLAMP = 8;
+constexpr uint32_t OL_ROW = 8;                         // words of a pattern row: planes 0..3, clamp, L, two of padding (32 B)
+constexpr uint32_t OL_GROUP = OL_MAX_OLIGOS;           // oligos per pass: the table is read by scalar loads, nothing on the chip bounds it
+constexpr uint64_t OL_BUFFER_BYTES = 64ull << 20;      // budget of the site buffer: speed only, chosen without a measurement
+constexpr uint64_t OL_MAX_BASES = 1ull << 43;          // the batch-wide base index has 43 bits in a site key
+constexpr uint64_t OL_MAX_SITES = 1ull << 32;
+constexpr unsigned long long OL_NONE = ~0ull;
+// best-site key: mm << 58 | base index << 1 | strand; site key: oligo << 48 | base index << 5 | strand << 4 | mm
+constexpr uint32_t OL_BEST_MM_SHIFT = 58, OL_SITE_Q_SHIFT = 48, OL_SITE_IDX_SHIFT = 5;
+
+typedef const __attribute__((address_space(4))) uint32_t *ol_table_t;   // constant address space: uniform reads are scalar loads
+
+struct ScanArgs {
+    RunView v;                       // the tiles of this launch (runs of lmin bases or more; a "k-mer" is a window end)
+    const uint32_t *tab;             // [n_pat][OL_ROW] the pass's patterns: 2 q' + strand
+    uint32_t n_pat, q0;              // q0: the pass's first oligo
+    uint32_t lmin, max_mm;
+    uint64_t n_asm;
+    uint32_t *n_sites;               // [n_oligos][n_asm]
+    unsigned long long *best;        // [oligos of the pass][n_asm]
+    unsigned long long *buf;         // site keys of the chunk (nullptr: no list is wanted; the cursor still counts)
+    unsigned long long cap;
+    unsigned long long *cursor;      // sites appended (above cap: the chunk overflowed, it is redone)
+};
+
+// the last 32 bases a lane has read, as the plane of their low bits and the plane of their high bits; bit 0 = the last base
+struct PlaneRoller {
+    const uint32_t *packed;
+    uint64_t pos = 0;
+    uint32_t w = 0, left = 0, lo = 0, hi = 0;
+    __device__ __forceinline__ explicit PlaneRoller(const uint32_t *packed_bases) : packed(packed_bases) {}
+    __device__ __forceinline__ void start(uint64_t pos0)   // (reads the word that holds base pos0)
+    {
+        pos = pos0;
+        w = packed[pos >> 4] >> (2 * (uint32_t)(pos & 15));
+        left = 16 - (uint32_t)(pos & 15);
+    }
+    __device__ __forceinline__ void roll()
+    {
+        if (left == 0) {
+            w = packed[pos >> 4];
+            left = 16;
+        }
+        lo = (lo << 1) | (w & 1u);
+        hi = (hi << 1) | ((w >> 1) & 1u);
+        w >>= 2;
+        --left;
+        ++pos;
+    }
+};
+
+__device__ __forceinline__ uint32_t ol_select(uint32_t s, uint32_t one, uint32_t zero)
+{
+    return (s & one) | (~s & zero);
+}
+
+// the mismatch bits of a window (its two planes) against a pattern (its four mismatch planes)
+__device__ __forceinline__ uint32_t ol_mismatches(uint32_t lo, uint32_t hi, uint32_t n0, uint32_t n1, uint32_t n2, uint32_t n3)
+{
+    return ol_select(hi, ol_select(lo, n3, n2), ol_select(lo, n1, n0));
+}
+
+__global__ __launch_bounds__(KW_TPB) void k_ol_scan(ScanArgs g)
+{
+    const uint32_t lane = threadIdx.x % KW_WAVE;
+    uint32_t r, n_mine;
+    uint64_t first;
+    if (!wave_tile(g.v, lane, r, first, n_mine)) return;   // (the whole wave)
+    if (g.buf && *(volatile unsigned long long *)g.cursor > g.cap) return;   // (the whole wave: the chunk has overflowed, it is redone anyway)
+    const uint32_t a = g.v.run_asm[r];
+    const uint64_t run_base = g.v.run_base[r];
+    const uint64_t e0 = first + g.lmin - 1;   // the offset in the run of the lane's first window end
+    uint32_t lo[KW_L], hi[KW_L];
+    PlaneRoller R(g.v.packed);
+    if (n_mine) {
+        const uint32_t pre = e0 < OL_MAX_LEN - 1 ? (uint32_t)e0 : OL_MAX_LEN - 1;   // bases before the first end, bounded by the run's start
+        R.start(run_base + e0 - pre);
+        for (uint32_t i = 0; i < pre; ++i) R.roll();
+    }
+#pragma unroll
+    for (uint32_t j = 0; j < KW_L; ++j) {
+        if (j < n_mine) R.roll();
+        lo[j] = R.lo;
+        hi[j] = R.hi;
+    }
+    const uint32_t mine = (1u << n_mine) - 1;   // (n_mine <= 16)
+    const ol_table_t tab = (ol_table_t)g.tab;
+    for (uint32_t p = 0; p < g.n_pat; ++p) {    // (uniform)
+        const ol_table_t row = tab + (uint64_t)p * OL_ROW;
+        const uint32_t n0 = row[0], n1 = row[1], n2 = row[2], n3 = row[3], clamp = row[4], len = row[5];
+        uint32_t cand = 0;
+#pragma unroll
+        for (uint32_t j = 0; j < KW_L; ++j) {
+            const uint32_t x = ol_mismatches(lo[j], hi[j], n0, n1, n2, n3);
+            cand |= ((uint32_t)__popc(x) <= g.max_mm && !(x & clamp)) ? 1u << j : 0u;
+        }
+        if (!__ballot(cand != 0)) continue;     // (uniform) candidates are rare
+        // a window that ends at offset e of its run holds the oligo iff e + 1 >= len
+        cand &= mine;
+        if (e0 + 1 < len) {
+            const uint32_t short_by = len - 1 - (uint32_t)e0;   // (1..31) the lane's first short_by ends lie too near the run's start
+            cand &= short_by >= KW_L ? 0u : ~((1u << short_by) - 1);
+        }
+        const WaveRange w = wave_append(g.cursor, lane, (uint32_t)__popc(cand));
+        if (!w.total) continue;                 // (uniform)
+        const bool store = g.buf && w.base + w.total <= g.cap;   // (uniform) overflow: the host reads it from the cursor
+        const uint32_t q_local = p >> 1, strand = p & 1;
+        uint32_t at = 0;
+#pragma unroll
+        for (uint32_t j = 0; j < KW_L; ++j) {
+            if (!((cand >> j) & 1)) continue;
+            const unsigned long long mm = (unsigned long long)__popc(ol_mismatches(lo[j], hi[j], n0, n1, n2, n3));
+            const unsigned long long idx = run_base + e0 + j + 1 - len;   // the batch-wide index of the site's first base
+            atomicAdd(g.n_sites + (uint64_t)(g.q0 + q_local) * g.n_asm + a, 1u);
+            atomicMin(g.best + (uint64_t)q_local * g.n_asm + a, (mm << OL_BEST_MM_SHIFT) | (idx << 1) | strand);
+            if (store)
+                g.buf[w.base + w.offset + at] = ((unsigned long long)(g.q0 + q_local) << OL_SITE_Q_SHIFT) | (idx << OL_SITE_IDX_SHIFT) | (strand << 4) | mm;
+            ++at;
+        }
+    }
+}
+
+// the last run whose first base is <= idx
+__device__ __forceinline__ uint32_t ol_run_of(const uint64_t *__restrict__ run_base, uint32_t n_runs, uint64_t idx)
+{
+    uint32_t lo = 0, hi = n_runs;
+    while (lo + 1 < hi) {
+        const uint32_t mid = lo + ((hi - lo) >> 1);
+        if (run_base[mid] <= idx) lo = mid; else hi = mid;
+    }
+    return lo;
+}
+
+// cell i of the pass (oligo q0 + i / n_asm, assembly i % n_asm) with a site: the four fields of its best one
+__global__ __launch_bounds__(SCR_TPB) void k_ol_resolve(uint64_t base, uint64_t end, const unsigned long long *__restrict__ best, uint64_t cell0, RunView v,
+                                                        uint32_t *__restrict__ mm, uint32_t *__restrict__ rec, uint32_t *__restrict__ pos,
+                                                        uint32_t *__restrict__ strand)
+{
+    const uint64_t i = base + (uint64_t)blockIdx.x * SCR_TPB + threadIdx.x;
+    if (i >= end) return;
+    const unsigned long long key = best[i];
+    if (key == OL_NONE) return;   // (the fields hold 0xFFFFFFFF)
+    const uint64_t idx = (key & ((1ull << OL_BEST_MM_SHIFT) - 1)) >> 1;
+    const uint32_t r = ol_run_of(v.run_base, v.n_runs, idx);
+    mm[cell0 + i] = (uint32_t)(key >> OL_BEST_MM_SHIFT);
+    rec[cell0 + i] = v.run_rec[r];
+    pos[cell0 + i] = v.run_pos[r] + (uint32_t)(idx - v.run_base[r]);
+    strand[cell0 + i] = (uint32_t)(key & 1);
+}
+
+__global__ __launch_bounds__(SCR_TPB) void k_ol_decode(uint64_t base, uint64_t end, const uint64_t *__restrict__ keys, RunView v, uint32_t *__restrict__ asm_out,
+                                                       uint32_t *__restrict__ rec, uint32_t *__restrict__ pos)
+{
+    const uint64_t i = base + (uint64_t)blockIdx.x * SCR_TPB + threadIdx.x;
+    if (i >= end) return;
+    const uint64_t idx = (keys[i] & ((1ull << OL_SITE_Q_SHIFT) - 1)) >> OL_SITE_IDX_SHIFT;
+    const uint32_t r = ol_run_of(v.run_base, v.n_runs, idx);
+    asm_out[i] = v.run_asm[r];
+    rec[i] = v.run_rec[r];
+    pos[i] = v.run_pos[r] + (uint32_t)(idx - v.run_base[r]);
+}
+
+// ---- host: the oligos -------------------------------------------------------------------------------------------------------------
+// the set of bases a letter stands for (bit b: base b of A C G T), 0: no letter of an oligo
+uint32_t iupac_set(unsigned char c)
+{
+    switch (c | 0x20) {
+    case 'a': return 1;
+    case 'c': return 2;
+    case 'g': return 4;
+    case 't': case 'u': return 8;
+    case 'r': return 1 | 4;
+    case 'y': return 2 | 8;
+    case 's': return 2 | 4;
+    case 'w': return 1 | 8;
+    case 'k': return 4 | 8;
+    case 'm': return 1 | 2;
+    case 'b': return 2 | 4 | 8;
+    case 'd': return 1 | 4 | 8;
+    case 'h': return 1 | 2 | 8;
+    case 'v': return 1 | 2 | 4;
+    case 'n': return 15;
+    default: return 0;
+    }
+}
+
+inline uint32_t complement_set(uint32_t s)   // A <-> T, C <-> G
+{
+    return ((s & 1) << 3) | ((s & 2) << 1) | ((s & 4) >> 1) | ((s & 8) >> 3);
+}
+
+// what a call says about its oligos by itself, before a device is touched; returns the shortest length
+uint32_t check_oligos(const uint64_t *offsets, const char *blob, uint64_t n, uint64_t max_mm, uint64_t three_prime)
+{
+    if (n < 1 || n > OL_MAX_OLIGOS) raise(SW_ERR_VALUE, "oligo hits: %llu oligos; 1..%u are taken", (unsigned long long)n, OL_MAX_OLIGOS);
+    if (!offsets || !blob) raise(SW_ERR_VALUE, "oligo hits: a NULL handle or array");
+    if (offsets[0] != 0) raise(SW_ERR_VALUE, "oligo hits: offsets must start at 0");
+    uint32_t lmin = OL_MAX_LEN;
+    for (uint64_t q = 0; q < n; ++q) {
+        if (offsets[q] > offsets[q + 1]) raise(SW_ERR_VALUE, "oligo hits: offsets must be non-decreasing (oligo %llu)", (unsigned long long)q);
+        const uint64_t len = offsets[q + 1] - offsets[q];
+        if (len < OL_MIN_LEN || len > OL_MAX_LEN)
+            raise(SW_ERR_VALUE, "oligo hits: oligo %llu has %llu letters; %u..%u are taken", (unsigned long long)q, (unsigned long long)len, OL_MIN_LEN, OL_MAX_LEN);
+        for (uint64_t i = offsets[q]; i < offsets[q + 1]; ++i)
+            if (!iupac_set((unsigned char)blob[i]))
+                raise(SW_ERR_VALUE, "oligo hits: oligo %llu holds byte 0x%02x at %llu, which is no IUPAC letter", (unsigned long long)q,
+                      (unsigned)(unsigned char)blob[i], (unsigned long long)(i - offsets[q]));
+        lmin = std::min<uint32_t>(lmin, (uint32_t)len);
+    }
+    if (max_mm > OL_MAX_MM || max_mm >= lmin)
+        raise(SW_ERR_VALUE, "oligo hits: max_mismatch must lie in 0..%u and below the shortest oligo's %u letters (got %llu)", OL_MAX_MM, lmin,
+              (unsigned long long)max_mm);
+    if (three_prime > OL_MAX_CLAMP) raise(SW_ERR_VALUE, "oligo hits: three_prime must lie in 0..%u (got %llu)", OL_MAX_CLAMP, (unsigned long long)three_prime);
+    return lmin;
+}
+
+// the two rows of oligo `text`: strand 0, strand 1
+void pattern_rows(const char *text, uint32_t len, uint32_t clamp, uint32_t *rows)
+{
+    memset(rows, 0, 2 * OL_ROW * sizeof(uint32_t));
+    for (uint32_t t = 0; t < len; ++t) {
+        const uint32_t s0 = iupac_set((unsigned char)text[len - 1 - t]);       // strand 0: position len - 1 - t faces the base t before the end
+        const uint32_t s1 = complement_set(iupac_set((unsigned char)text[t])); // strand 1: P1[len - 1 - t] = complement of P0[t]
+        for (uint32_t b = 0; b < 4; ++b) {
+            if (!((s0 >> b) & 1)) rows[b] |= 1u << t;
+            if (!((s1 >> b) & 1)) rows[OL_ROW + b] |= 1u << t;
+        }
+    }
+    const uint32_t c = clamp ? (uint32_t)((1ull << clamp) - 1) : 0u;   // (clamp <= 8 <= len)
+    rows[4] = c;                       // strand 0: the oligo's last `clamp` positions = the window's last bases
+    rows[OL_ROW + 4] = c << (len - clamp);   // strand 1: its first positions = the window's first bases
+    rows[5] = rows[OL_ROW + 5] = len;
+}
+
+}  // namespace
+}  // namespace sw
+
+struct sw_oligos {
+    int device = 0;
+    uint64_t nq = 0, n_asm = 0, max_mm = 0, three_prime = 0;
+    sw::DevArray<uint32_t> field[5];       // [nq][n_asm] n_sites, best_mm, best_record, best_pos, best_strand
+    bool has_sites = false;
+    uint64_t n_list = 0;
+    sw::DevArray<uint64_t> keys;           // [n_list] the site keys, ascending
+    sw::DevArray<uint32_t> s_asm, s_rec, s_pos;
+    uint64_t counters[8] = {};             // sw_oligos_stats
+    double ms[2] = {};                     // scan, order
+};
+
+namespace sw {
+namespace {
+
+void batch_oligo_hits(const sw_batch &b, const uint64_t *offsets, const char *blob, uint64_t nq, uint32_t lmin, uint32_t max_mm, uint32_t three_prime,
+                      bool want_sites, hipStream_t stream, sw_oligos &o)
+{
+    const HostBatch &h = b.host;
+    const uint64_t n_asm = h.n_assemblies, cells = nq * n_asm;
+    if (h.rec_len.size() && !b.d_packed.p) raise(SW_ERR_VALUE, "oligo hits: the batch holds no packed bases (it must be resident)");
+    if ((uint64_t)h.packed_words32() * 16 >= OL_MAX_BASES) raise(SW_ERR_RUNTIME, "oligo hits: the batch has 2^43 bases or more");
+    o.nq = nq;
+    o.n_asm = n_asm;
+    o.max_mm = max_mm;
+    o.three_prime = three_prime;
+    o.has_sites = want_sites;
+    for (int f = 0; f < 5; ++f) {
+        o.field[f].alloc(cells);
+        if (cells) SW_HIP(hipMemsetAsync(o.field[f].p, f ? 0xFF : 0, cells * 4, stream));
+    }
+    // ---- the runs of lmin bases or more: a tile's "k-mers" are window ends (kmer_walk.hpp) ----
+    RunTiles T;
+    build_run_tiles(h, lmin, "oligo hits", T);
+    uint64_t group = OL_GROUP, budget = OL_BUFFER_BYTES;
+    if (const char *e = SW_TEST_GETENV("SEQWIN_AMD_OLIGO_GROUP")) group = std::min<uint64_t>(std::max<uint64_t>(env_u64(e, group), 1), OL_GROUP);
+    if (const char *e = SW_TEST_GETENV("SEQWIN_AMD_OLIGO_BUFFER_KB")) budget = env_u64(e, budget >> 10) << 10;
+    group = std::min<uint64_t>(group, nq);
+    uint64_t cap = std::min<uint64_t>(std::max<uint64_t>(budget / 8, 1), OL_MAX_SITES);
+    const uint32_t blocks_max = launch_blocks("SEQWIN_AMD_OLIGO_MAX_BLOCKS");   // the scan kernel's; the switch (test library) lowers it
+    uint64_t passes = 0, chunks = 0, launches = 0, hits = 0, grows = 0, splits = 0, windows = 0, comparisons = 0;
+    std::vector<DevArray<uint64_t>> lists;   // the chunks' site keys, in the order the chunks ended
+    Event e0, e1, e2;
+    SW_HIP(hipEventRecord(e0, stream));
+    DevRunTiles runs(T, b.d_packed.p, stream, true);
+    if (T.tiles && cells) {
+        std::vector<uint32_t> rows_host(group * 2 * OL_ROW);
+        DevArray<uint32_t> tab(group * 2 * OL_ROW);
+        DevArray<unsigned long long> best(group * n_asm), d_cursor(1), buf;
+        if (want_sites) buf.alloc(cap);
+        ScanArgs g{};
+        g.tab = tab.p;
+        g.lmin = lmin;
+        g.max_mm = max_mm;
+        g.n_asm = n_asm;
+        g.n_sites = o.field[0].p;
+        g.best = best.p;
+        g.cursor = d_cursor.p;
+        uint64_t rows = n_asm;
+        for (uint64_t q0 = 0; q0 < nq; q0 += group, ++passes) {
+            const uint64_t qn = std::min<uint64_t>(group, nq - q0);
+            for (uint64_t q = 0; q < qn; ++q)
+                pattern_rows(blob + offsets[q0 + q], (uint32_t)(offsets[q0 + q + 1] - offsets[q0 + q]), three_prime, rows_host.data() + q * 2 * OL_ROW);
+            SW_HIP(hipMemcpyAsync(tab.p, rows_host.data(), qn * 2 * OL_ROW * 4, hipMemcpyHostToDevice, stream));
+            SW_HIP(hipMemsetAsync(best.p, 0xFF, qn * n_asm * 8, stream));
+            g.n_pat = (uint32_t)(2 * qn);
+            g.q0 = (uint32_t)q0;
+            for (uint64_t a0 = 0; a0 < n_asm;) {
+                const uint64_t a1 = std::min<uint64_t>(n_asm, a0 + rows);
+                SW_HIP(hipMemsetAsync(d_cursor.p, 0, 8, stream));
+                g.buf = buf.p;
+                g.cap = cap;
+                g.v = runs.view(T.asm_tile_off[a0], T.asm_tile_off[a1]);
+                launches += launch_tiles(k_ol_scan, g, blocks_max, stream);
+                unsigned long long n = 0;
+                SW_HIP(hipMemcpyAsync(&n, d_cursor.p, 8, hipMemcpyDeviceToHost, stream));
+                SW_HIP(hipStreamSynchronize(stream));   // (the pattern rows of the host are free again, too)
+                if (want_sites && n > cap) {
+                    // the chunk's counts are partial: its columns of this pass's rows are cleared (the best sites are minima: a redo changes nothing)
+                    SW_HIP(hipMemset2DAsync(o.field[0].p + q0 * n_asm + a0, n_asm * 4, 0, (a1 - a0) * 4, qn, stream));
+                    if (a1 - a0 > 1) {   // redone in two halves: the first now, the second is the next chunk
+                        rows = (a1 - a0 + 1) / 2;
+                        ++splits;
+                    } else {             // one assembly above the budget: the buffer doubles
+                        if (cap >= OL_MAX_SITES) raise(SW_ERR_RUNTIME, "oligo hits: assembly %llu alone has 2^32 sites or more", (unsigned long long)a0);
+                        cap = std::min<uint64_t>(cap * 2, OL_MAX_SITES);
+                        buf.alloc(cap);
+                        ++grows;
+                    }
+                    continue;
+                }
+                hits += n;
+                windows += T.asm_kmers[a1] - T.asm_kmers[a0];
+                comparisons += (T.asm_kmers[a1] - T.asm_kmers[a0]) * 2 * qn;
+                ++chunks;
+                if (want_sites && n) {
+                    if (hits >= OL_MAX_SITES) raise(SW_ERR_RUNTIME, "oligo hits: a site list of 2^32 entries or more");
+                    lists.emplace_back((size_t)n);
+                    SW_HIP(hipMemcpyAsync(lists.back().p, buf.p, n * 8, hipMemcpyDeviceToDevice, stream));
+                }
+                a0 = a1;
+            }
+            launch_1d(k_ol_resolve, qn * n_asm, stream, (const unsigned long long *)best.p, q0 * n_asm, runs.view(), o.field[1].p, o.field[2].p, o.field[3].p,
+                      o.field[4].p);
+        }
+    }
+    SW_HIP(hipEventRecord(e1, stream));
+    // ---- the site list: all chunks' keys in one ascending order = (oligo, assembly, record, pos, strand) ----
+    if (want_sites && hits) {
+        DevArray<uint64_t> ka(hits), kb(hits);
+        uint64_t at = 0;
+        for (DevArray<uint64_t> &l : lists) {
+            SW_HIP(hipMemcpyAsync(ka.p + at, l.p, l.n * 8, hipMemcpyDeviceToDevice, stream));
+            at += l.n;
+        }
+        if (at != hits) raise(SW_ERR_RUNTIME, "internal error: the chunks' site lists do not add up");
+        uint64_t *kp = ka.p, *ap = kb.p;
+        sort_all_bits(kp, ap, hits, stream);
+        lists.clear();
+        if (kp != ka.p) std::swap(ka, kb);
+        o.keys = std::move(ka);
+        o.n_list = hits;
+        o.s_asm.alloc(hits);
+        o.s_rec.alloc(hits);
+        o.s_pos.alloc(hits);
+        launch_1d(k_ol_decode, hits, stream, (const uint64_t *)o.keys.p, runs.view(), o.s_asm.p, o.s_rec.p, o.s_pos.p);
+    }
+    SW_HIP(hipEventRecord(e2, stream));
+    SW_HIP(hipStreamSynchronize(stream));   // (the temporaries go back to the pool behind the kernels)
+    float ms = 0;
+    SW_HIP(hipEventElapsedTime(&ms, e0, e1));
+    o.ms[0] = ms;
+    SW_HIP(hipEventElapsedTime(&ms, e1, e2));
+    o.ms[1] = ms;
+    const uint64_t cn[8] = {windows, passes, chunks, launches, hits, grows, splits, comparisons};
+    memcpy(o.counters, cn, sizeof cn);
+}
+
+}  // namespace
+}  // namespace sw
+
+using namespace sw;
+
+extern "C" {
+
+int sw_batch_oligo_hits(const sw_batch *batch, const uint64_t *offsets, const char *blob, uint64_t n_oligos, uint64_t max_mismatch, uint64_t three_prime,
+                        int want_sites, void *stream, sw_oligos **out)
+{
+    return guarded([&] {
+        const uint32_t lmin = check_oligos(offsets, blob, n_oligos, max_mismatch, three_prime);
+        if (!batch || !out) raise(SW_ERR_VALUE, "oligo hits: a NULL handle or array");
+        require_device(batch->device, "the batch");
+        StreamScope scope((hipStream_t)stream);
+        std::unique_ptr<sw_oligos> o(new sw_oligos);
+        o->device = batch->device;
+        batch_oligo_hits(*batch, offsets, blob, n_oligos, lmin, (uint32_t)max_mismatch, (uint32_t)three_prime, want_sites != 0, (hipStream_t)stream, *o);
+        *out = o.release();
+    });
+}
+
+int sw_oligos_sizes(const sw_oligos *h, uint64_t *n_oligos, uint64_t *n_assemblies, uint64_t *max_mismatch, uint64_t *three_prime)
+{
+    return guarded([&] {
+        if (!h) raise(SW_ERR_VALUE, "oligo hits: a NULL handle");
+        if (n_oligos) *n_oligos = h->nq;
+        if (n_assemblies) *n_assemblies = h->n_asm;
+        if (max_mismatch) *max_mismatch = h->max_mm;
+        if (three_prime) *three_prime = h->three_prime;
+    });
+}
+
+int sw_oligos_block(const sw_oligos *h, uint64_t field, uint64_t r0, uint64_t r1, uint64_t c0, uint64_t c1, uint32_t *out)
+{
+    return guarded([&] {
+        if (!h) raise(SW_ERR_VALUE, "oligo hits: a NULL handle");
+        if (field > 4) raise(SW_ERR_VALUE, "oligo hits: field %llu; 0 n_sites, 1 best_mm, 2 best_record, 3 best_pos, 4 best_strand", (unsigned long long)field);
+        if (r0 > r1 || r1 > h->nq || c0 > c1 || c1 > h->n_asm)
+            raise(SW_ERR_VALUE, "oligo hits: rows [%llu, %llu) x columns [%llu, %llu) lie outside the %llu oligos x %llu assemblies", (unsigned long long)r0,
+                  (unsigned long long)r1, (unsigned long long)c0, (unsigned long long)c1, (unsigned long long)h->nq, (unsigned long long)h->n_asm);
+        const uint64_t nr = r1 - r0, nc = c1 - c0;
+        if (!nr || !nc) return;
+        if (!out) raise(SW_ERR_VALUE, "oligo hits: a NULL handle or array");
+        require_device(h->device, "the oligo hits");
+        SW_HIP(hipMemcpy2D(out, nc * 4, h->field[field].p + r0 * h->n_asm + c0, h->n_asm * 4, nc * 4, nr, hipMemcpyDeviceToHost));
+    });
+}
+
+int sw_oligos_sites_size(const sw_oligos *h, uint64_t *n_sites_total)
+{
+    return guarded([&] {
+        if (!h) raise(SW_ERR_VALUE, "oligo hits: a NULL handle");
+        if (!h->has_sites) raise(SW_ERR_VALUE, "oligo hits: these hits were made without the site list");
+        if (n_sites_total) *n_sites_total = h->n_list;
+    });
+}
+
+int sw_oligos_sites(const sw_oligos *h, uint64_t *cell_offsets, uint32_t *oligo, uint32_t *assembly, uint32_t *record, uint32_t *pos, uint32_t *strand,
+                    uint32_t *mm)
+{
+    return guarded([&] {
+        if (!h) raise(SW_ERR_VALUE, "oligo hits: a NULL handle");
+        if (!h->has_sites) raise(SW_ERR_VALUE, "oligo hits: these hits were made without the site list");
+        const uint64_t n = h->n_list, cells = h->nq * h->n_asm;
+        if (!cell_offsets || (n && (!oligo || !assembly || !record || !pos || !strand || !mm))) raise(SW_ERR_VALUE, "oligo hits: a NULL handle or array");
+        require_device(h->device, "the oligo hits");
+        std::vector<uint32_t> counts(cells);
+        if (cells) SW_HIP(hipMemcpy(counts.data(), h->field[0].p, cells * 4, hipMemcpyDeviceToHost));
+        cell_offsets[0] = 0;
+        for (uint64_t c = 0; c < cells; ++c) cell_offsets[c + 1] = cell_offsets[c] + counts[c];
+        if (cell_offsets[cells] != n) raise(SW_ERR_RUNTIME, "internal error: the cells' site counts do not add up to the list");
+        if (!n) return;
+        std::vector<uint64_t> keys(n);
+        SW_HIP(hipMemcpy(keys.data(), h->keys.p, n * 8, hipMemcpyDeviceToHost));
+        SW_HIP(hipMemcpy(assembly, h->s_asm.p, n * 4, hipMemcpyDeviceToHost));
+        SW_HIP(hipMemcpy(record, h->s_rec.p, n * 4, hipMemcpyDeviceToHost));
+        SW_HIP(hipMemcpy(pos, h->s_pos.p, n * 4, hipMemcpyDeviceToHost));
+        for (uint64_t i = 0; i < n; ++i) {
+            oligo[i] = (uint32_t)(keys[i] >> OL_SITE_Q_SHIFT);
+            strand[i] = (uint32_t)(keys[i] >> 4) & 1;
+            mm[i] = (uint32_t)keys[i] & 15;
+        }
+    });
+}
+
+int sw_oligos_stats(const sw_oligos *h, uint64_t *counters, double *ms)
+{
+    return guarded([&] {
+        if (!h) raise(SW_ERR_VALUE, "oligo hits: a NULL handle");
+        if (counters) memcpy(counters, h->counters, sizeof h->counters);
+        if (ms) memcpy(ms, h->ms, sizeof h->ms);
+    });
+}
+
+void sw_oligos_free(sw_oligos *h)
+{
+    delete h;
+}
+
+}  // extern "C"

@@ -256,6 +256,24 @@ class Batch:
         check(fn(self._h, _ptr(offs), blob, c_u64(nq), c_u64(int(kmerlen)), ctypes.byref(h)))
         return BestHits(h, aligned=bool(align))
 
+    def oligo_hits(self, oligos, max_mismatch: int = 0, three_prime: int = 0, sites: bool = False, stream: int = 0) -> "OligoHits":
+        """Every place in every assembly where an oligo (a list of ``str`` or ``bytes``: primers, probes) binds with at most
+        ``max_mismatch`` mismatches, on either strand -- exhaustively, every window of the batch against every oligo, no seed
+        (csrc/oligo.hip).  An oligo is 8..32 letters in either case: ``ACGT``, ``U`` (= T) or an IUPAC code
+        ``RYSWKMBDHVN``; every position is a set of bases.  Strand 0 is the oligo, strand 1 its reverse complement.  A site is a window
+        inside one valid run of a record, ``mm`` the number of its bases outside the set they face; a hit has ``mm <= max_mismatch``
+        (0..8, below the shortest oligo) and no mismatch among the ``three_prime`` (0..8) bases at the oligo's 3' end.  An oligo that
+        equals its reverse complement hits twice at one place.  ``sites=True`` also keeps the list of all hits.  Not BLAST and not a
+        thermodynamic model: no Tm, no dG, no e-values.  ValueError for anything else, before a device is touched."""
+        from .oligos import check_oligos
+        qs = check_oligos(oligos, max_mismatch, three_prime)
+        offs = np.zeros(len(qs) + 1, np.uint64)
+        np.cumsum([len(q) for q in qs], out=offs[1:])
+        h = c_vp()
+        check(lib.sw_batch_oligo_hits(self._h, _ptr(offs), b"".join(qs), c_u64(len(qs)), c_u64(int(max_mismatch)), c_u64(int(three_prime)),
+                                      ctypes.c_int(1 if sites else 0), c_vp(stream), ctypes.byref(h)))
+        return OligoHits(h, [len(q) for q in qs], bool(sites))
+
     def fetch(self, intervals, stats: bool = False):
         """The text of ``intervals`` (INTERVAL_DTYPE or an (n, 3) array of record, start, stop; ``record`` is the batch's global
         record index), decoded from the resident packed bases (csrc/seqs.hip): ``(offsets, blob, inexact)`` -- interval i is
@@ -918,6 +936,97 @@ class Screen:
     def close(self) -> None:
         if self._h:
             lib.sw_screen_free(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+SITE_FIELDS = ("oligo", "assembly", "record", "pos", "strand", "mm")
+
+
+class OligoHits:
+    """The sites of a list of oligos in every assembly of a batch, resident on the device (:meth:`Batch.oligo_hits`; csrc/oligo.hip,
+    DESIGN.md section 3.2j): per (oligo, assembly) ``n_sites``, the number of hits on both strands, and the hit that is least in the
+    order (mm, record, pos, strand) as ``best_mm``, ``best_record`` (global), ``best_pos`` and ``best_strand`` -- NO_HIT without a
+    hit.  It has no counterpart in the reference, is not BLAST, is no thermodynamic model and fills none of ``MarkerMetrics``.  A
+    single-device object on a resident batch.  ``rows`` (oligos) / ``cols`` (assemblies) are None (all), a ``(lo, hi)`` pair, a slice
+    or a range.  Made with ``sites=True`` it also holds the list of all hits."""
+
+    def __init__(self, handle: c_vp, lengths, sites: bool = False):
+        self._h = handle
+        self.lengths = np.asarray(lengths, np.uint32)
+        self._sites = sites
+
+    def sizes(self):
+        """(oligos, assemblies, max_mismatch, three_prime)"""
+        v = [c_u64() for _ in range(4)]
+        check(lib.sw_oligos_sizes(self._h, *[ctypes.byref(x) for x in v]))
+        return tuple(x.value for x in v)
+
+    def _block(self, field: int, rows, cols) -> np.ndarray:
+        nq, na, _, _ = self.sizes()
+        (r0, r1), (c0, c1) = _block_range(rows, nq), _block_range(cols, na)
+        out = np.empty((max(r1 - r0, 0), max(c1 - c0, 0)), np.uint32)
+        check(lib.sw_oligos_block(self._h, c_u64(field), c_u64(r0), c_u64(r1), c_u64(c0), c_u64(c1), _ptr(out)))
+        return out
+
+    def n_sites(self, rows=None, cols=None) -> np.ndarray:
+        """uint32[rows, cols]: the hits of the oligo in the assembly, both strands together; 0: none."""
+        return self._block(0, rows, cols)
+
+    def best_mm(self, rows=None, cols=None) -> np.ndarray:
+        return self._block(1, rows, cols)
+
+    def best_record(self, rows=None, cols=None) -> np.ndarray:
+        return self._block(2, rows, cols)
+
+    def best_pos(self, rows=None, cols=None) -> np.ndarray:
+        return self._block(3, rows, cols)
+
+    def best_strand(self, rows=None, cols=None) -> np.ndarray:
+        return self._block(4, rows, cols)
+
+    def sites(self) -> dict:
+        """Every hit, ascending by (oligo, assembly, record, pos, strand), as parallel uint32 arrays ``oligo``, ``assembly``,
+        ``record``, ``pos``, ``strand``, ``mm``; ``cell_offsets`` (uint64[oligos * assemblies + 1]) bounds the hits of every pair."""
+        if not self._sites:
+            raise ValueError("these oligo hits were made without sites=True")
+        nq, na, _, _ = self.sizes()
+        n = c_u64()
+        check(lib.sw_oligos_sites_size(self._h, ctypes.byref(n)))
+        offs = np.empty(nq * na + 1, np.uint64)
+        cols = [np.empty(n.value, np.uint32) for _ in SITE_FIELDS]
+        check(lib.sw_oligos_sites(self._h, _ptr(offs), *[_ptr(a) if n.value else None for a in cols]))
+        out = dict(zip(SITE_FIELDS, cols))
+        out["cell_offsets"] = offs
+        return out
+
+    def intervals(self) -> np.ndarray:
+        """INTERVAL_DTYPE ``(record, pos, pos + L)`` of every hit, in the list's order, as :meth:`Batch.fetch` takes them (the text
+        of a strand-1 hit faces the oligo's reverse complement)."""
+        S = self.sites()
+        iv = np.empty(len(S["oligo"]), INTERVAL_DTYPE)
+        iv["record"], iv["start"], iv["stop"] = S["record"], S["pos"], S["pos"] + self.lengths[S["oligo"]]
+        return iv
+
+    def stats(self) -> dict:
+        """``windows`` (window ends scanned, summed over the passes), ``passes`` (groups of oligos), ``chunks`` (of assemblies),
+        ``launches``, ``hits``, ``buffer_doublings``, ``chunk_splits``, ``comparisons`` (window x oligo x strand), ``scan_ms`` and
+        ``order_ms`` (HIP events)."""
+        c = (c_u64 * 8)()
+        ms = (ctypes.c_double * 2)()
+        check(lib.sw_oligos_stats(self._h, c, ms))
+        d = dict(zip(("windows", "passes", "chunks", "launches", "hits", "buffer_doublings", "chunk_splits", "comparisons"), (int(x) for x in c)))
+        d.update(scan_ms=ms[0], order_ms=ms[1])
+        return d
+
+    def close(self) -> None:
+        if self._h:
+            lib.sw_oligos_free(self._h)
             self._h = None
 
     def __del__(self):

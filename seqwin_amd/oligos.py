@@ -1,0 +1,133 @@
+"""Primers and probes on the oligo search of :meth:`seqwin_amd.device.Batch.oligo_hits` (csrc/oligo.hip):
+the check of the oligos themselves, the products of primer pairs and two summaries.  NumPy on the site list; the list is small.
+
+None of this has a counterpart in the reference.  It is not BLAST and not a thermodynamic model -- no Tm, no dG, no e-values: a
+site is a window with at most ``max_mismatch`` mismatches under IUPAC sets, a product is two sites that face each other at a
+distance inside the caller's bounds.  The names are deliberately not those of ``MarkerMetrics``.
+"""
+from __future__ import annotations
+
+import numpy as np
+
+MIN_LEN, MAX_LEN, MAX_OLIGOS, MAX_MISMATCH, MAX_THREE_PRIME = 8, 32, 4096, 8, 8
+IUPAC = {"A": "A", "C": "C", "G": "G", "T": "T", "U": "T", "R": "AG", "Y": "CT", "S": "CG", "W": "AT", "K": "GT", "M": "AC", "B": "CGT",
+         "D": "AGT", "H": "ACT", "V": "ACG", "N": "ACGT"}
+AMPLICON_FIELDS = ("pair", "assembly", "record", "start", "end", "orientation", "mm_f", "mm_r")
+
+
+def check_oligos(oligos, max_mismatch: int = 0, three_prime: int = 0):
+    """The oligos as a list of ``bytes``, after the checks the library makes again: 1..4096 oligos of 8..32 IUPAC letters (either
+    case, ``U`` = ``T``), ``max_mismatch`` in 0..8 and below the shortest oligo, ``three_prime`` in 0..8.  ValueError otherwise."""
+    if isinstance(oligos, (str, bytes, bytearray)):
+        raise ValueError("oligos must be a list of str or bytes, not one string")
+    out = []
+    for q in oligos:
+        try:
+            out.append(q.encode("ascii") if isinstance(q, str) else bytes(q))
+        except UnicodeEncodeError:
+            raise ValueError(f"oligo {len(out)} holds a character that is no IUPAC letter") from None
+    if not 1 <= len(out) <= MAX_OLIGOS:
+        raise ValueError(f"{len(out)} oligos; 1..{MAX_OLIGOS} are taken")
+    for i, q in enumerate(out):
+        if not MIN_LEN <= len(q) <= MAX_LEN:
+            raise ValueError(f"oligo {i} has {len(q)} letters; {MIN_LEN}..{MAX_LEN} are taken")
+        for j, c in enumerate(q):
+            if chr(c).upper() not in IUPAC:
+                raise ValueError(f"oligo {i} holds byte 0x{c:02x} at {j}, which is no IUPAC letter")
+    shortest = min(len(q) for q in out)
+    if int(max_mismatch) != max_mismatch or not 0 <= max_mismatch <= MAX_MISMATCH or max_mismatch >= shortest:
+        raise ValueError(f"max_mismatch must lie in 0..{MAX_MISMATCH} and below the shortest oligo's {shortest} letters (got {max_mismatch})")
+    if int(three_prime) != three_prime or not 0 <= three_prime <= MAX_THREE_PRIME:
+        raise ValueError(f"three_prime must lie in 0..{MAX_THREE_PRIME} (got {three_prime})")
+    return out
+
+
+def _sites(hits):
+    return hits if isinstance(hits, dict) else hits.sites()
+
+
+def amplicons(hits, lengths, pairs, min_len: int, max_len: int, n_assemblies=None):
+    """The products of primer pairs on a site list.  ``hits`` is an :class:`~seqwin_amd.device.OligoHits` made with ``sites=True`` or
+    its ``sites()`` dict; ``lengths[q]`` the length of oligo q; ``pairs`` an (n, 2) array of ``(f, r)`` oligo indices.  Per pair and
+    record there are two orientations: ``+`` (0), a hit of f on strand 0 at ``pf`` and a hit of r on strand 1 at ``pr >= pf``, product
+    ``[pf, pr + L_r)``; ``-`` (1), a hit of r on strand 0 at ``pr`` and a hit of f on strand 1 at ``pf >= pr``, product ``[pr, pf +
+    L_f)``.  A product is kept iff ``min_len <= end - start <= max_len``; every combination counts; with ``f == r`` only ``+`` is
+    counted; a product may span invalid bases.  Returns ``(products, n_amplicons)``: a dict of arrays ``pair``, ``assembly``,
+    ``record``, ``start``, ``end``, ``orientation``, ``mm_f``, ``mm_r``, ordered by those fields in that order, and
+    ``n_amplicons[n_pairs, n_assemblies]`` (uint32).  ``n_assemblies`` is read from ``hits`` unless given."""
+    S = _sites(hits)
+    lengths = np.asarray(lengths, np.int64)
+    pairs = np.asarray(pairs, np.int64).reshape(-1, 2)
+    if n_assemblies is None:
+        if isinstance(hits, dict):
+            raise ValueError("n_assemblies must be given with a dict of sites")
+        n_assemblies = hits.sizes()[1]
+    if pairs.size and (pairs.min() < 0 or pairs.max() >= len(lengths)):
+        raise ValueError("a pair names an oligo outside lengths")
+    if min_len > max_len:
+        raise ValueError(f"min_len {min_len} exceeds max_len {max_len}")
+    oligo, strand = S["oligo"].astype(np.int64), S["strand"].astype(np.int64)
+    rec, pos, asm, mm = S["record"].astype(np.int64), S["pos"].astype(np.int64), S["assembly"].astype(np.int64), S["mm"].astype(np.int64)
+    cols = []
+
+    def side(q, s):
+        idx = np.nonzero((oligo == q) & (strand == s))[0]
+        return idx[np.lexsort((pos[idx], rec[idx]))]
+
+    def products(pi, first, last, len_last, orientation, f_is_first):
+        """every (site of `first` on strand 0, site of `last` on strand 1) of one record with a product length inside the bounds"""
+        if not len(first) or not len(last):
+            return
+        key_last = (rec[last] << 32) + pos[last]   # pr in [pf + max(min_len - L, 0), pf + max_len - L] of the same record
+        lo = np.searchsorted(key_last, (rec[first] << 32) + pos[first] + max(min_len - len_last, 0), "left")
+        hi = np.searchsorted(key_last, (rec[first] << 32) + np.minimum(pos[first] + max_len - len_last, 0xFFFFFFFF), "right")
+        n = np.maximum(hi - lo, 0)
+        a = np.repeat(np.arange(len(first)), n)
+        b = np.concatenate([np.arange(x, y) for x, y in zip(lo, hi) if y > x]) if n.sum() else np.zeros(0, np.int64)
+        i, j = first[a], last[b]
+        keep = pos[j] >= pos[i]
+        i, j = i[keep], j[keep]
+        start, end = pos[i], pos[j] + len_last
+        mf, mr = (mm[i], mm[j]) if f_is_first else (mm[j], mm[i])
+        cols.append(np.stack([np.full(len(i), pi), asm[i], rec[i], start, end, np.full(len(i), orientation), mf, mr], 1))
+
+    for pi, (f, r) in enumerate(pairs):
+        products(pi, side(f, 0), side(r, 1), int(lengths[r]), 0, True)
+        if f != r:
+            products(pi, side(r, 0), side(f, 1), int(lengths[f]), 1, False)
+    rows = np.concatenate(cols) if cols else np.zeros((0, 8), np.int64)
+    rows = rows[np.lexsort(rows.T[::-1])] if len(rows) else rows
+    out = {f: rows[:, i].astype(np.uint8 if f == "orientation" else np.uint32) for i, f in enumerate(AMPLICON_FIELDS)}
+    n_amp = np.zeros((len(pairs), int(n_assemblies)), np.uint32)
+    np.add.at(n_amp, (rows[:, 0], rows[:, 1]), 1)
+    return out, n_amp
+
+
+def oligo_summary(hits, n_tar: int) -> dict:
+    """Per oligo, over the targets (assemblies below ``n_tar``) and the others: ``f_tar`` / ``f_neg``, the fraction of them with a
+    hit (``nan`` for an empty side), and ``mean_best_mm_tar``, the mean ``best_mm`` over the targets with a hit (``nan`` without one)."""
+    n = np.asarray(hits.n_sites() if hasattr(hits, "n_sites") else hits["n_sites"])
+    best = np.asarray(hits.best_mm() if hasattr(hits, "best_mm") else hits["best_mm"])
+    if not 0 <= n_tar <= n.shape[1]:
+        raise ValueError(f"n_tar {n_tar} lies outside the {n.shape[1]} assemblies")
+    has = n > 0
+    with np.errstate(invalid="ignore", divide="ignore"):
+        f_tar = has[:, :n_tar].sum(1) / np.float64(n_tar) if n_tar else np.full(len(n), np.nan)
+        f_neg = has[:, n_tar:].sum(1) / np.float64(n.shape[1] - n_tar) if n.shape[1] > n_tar else np.full(len(n), np.nan)
+        s = np.where(has[:, :n_tar], best[:, :n_tar], 0).sum(1, dtype=np.float64)
+        mean = s / has[:, :n_tar].sum(1)
+    return dict(f_tar=f_tar, f_neg=f_neg, mean_best_mm_tar=mean)
+
+
+def assay_summary(n_amplicons, n_tar: int) -> dict:
+    """Per pair of :func:`amplicons`' ``n_amplicons``: ``f_tar_amplified`` (targets with a product), ``f_tar_single`` (targets with
+    exactly one) and ``f_neg_amplified`` (the others with a product), as fractions; ``nan`` for an empty side."""
+    n = np.asarray(n_amplicons)
+    if not 0 <= n_tar <= n.shape[1]:
+        raise ValueError(f"n_tar {n_tar} lies outside the {n.shape[1]} assemblies")
+    n_neg = n.shape[1] - n_tar
+    with np.errstate(invalid="ignore", divide="ignore"):
+        f_amp = (n[:, :n_tar] > 0).sum(1) / np.float64(n_tar) if n_tar else np.full(len(n), np.nan)
+        f_one = (n[:, :n_tar] == 1).sum(1) / np.float64(n_tar) if n_tar else np.full(len(n), np.nan)
+        f_neg = (n[:, n_tar:] > 0).sum(1) / np.float64(n_neg) if n_neg else np.full(len(n), np.nan)
+    return dict(f_tar_amplified=f_amp, f_tar_single=f_one, f_neg_amplified=f_neg)
