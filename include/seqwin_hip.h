@@ -635,6 +635,41 @@ int sw_hits_loci_local(const sw_hits *h, uint32_t *score, uint32_t *qstart, uint
 /* counters[6] and ms[1] as sw_batch_local_alignments', summed over the chunks, winners and loci together. */
 int sw_hits_local_stats(const sw_hits *h, uint64_t *counters, double *ms);
 
+/* ---- pileup: base counts per query position over the canonical alignments, by group (csrc/align.hip, the pile walk) ---------------
+ * By DESIGN.md section 3.2k (tests/tools/pileup_host.py restates it twice).  It is NOT BLAST and no multiple alignment: every pair
+ * is aligned to its query alone, and none of MarkerMetrics is filled.  The table is uint32 T[total query bases][n_groups][8], the
+ * queries one behind the other as in the call's CSR; the classes are A 0, C 1, G 2, T 3, N 4, DEL 5, INS 6, INS_BASES 7.  Walking a
+ * pair's script (section 3.2f) with pattern index i' and m = |query|: `=` / `X` add 1 to the class of the text base they face (an
+ * invalid one: N) at query position u = i' (strand 0) or m - 1 - i' with the base complemented (strand 1); `I` adds 1 to DEL at the
+ * same u; a maximal run of L `D` before pattern index i' adds 1 to INS and L to INS_BASES at u = i' (strand 0) or m - i' (strand 1),
+ * always 1 <= u <= m - 1.  depth[q][g] counts the pairs of query q piled into group g; A + C + G + T + N + DEL = depth at every
+ * position.  A pair is piled iff its label is below n_groups and dist * 1000 <= max_dist_permille * m; label 255 leaves it out.
+ * n_groups outside 1..8, max_dist_permille above 1000, a label in n_groups..254, (pairs of the call or assemblies of the batch)
+ * times the longest query reaching 2^32 -> SW_ERR_VALUE before a device is touched.  Nothing depends on the order of the pairs. */
+typedef struct sw_pileup sw_pileup; /* opaque: the device-resident table and depths of one call */
+/* sw_batch_infix_alignments without scripts -- the same six arrays, checks and errors, counters[8] and ms[3] -- whose walk also piles
+ * pair i into group pair_group[i]. */
+int sw_batch_infix_pileup(const sw_batch *b, const uint64_t *offsets, const char *blob, uint64_t n_queries, const sw_infix_pair *pairs, uint64_t n,
+                          const uint8_t *pair_group, uint64_t n_groups, uint64_t max_dist_permille, uint32_t *dist, uint32_t *end, uint32_t *a_start,
+                          uint32_t *nident, uint32_t *mismatch, uint32_t *gaps, sw_pileup **out, uint64_t *counters, double *ms);
+/* Best hits whose winners are piled, the winner of assembly a into group assembly_group[a].  seed_copies 0: the unique-seed route,
+ * else as sw_batch_best_hits_shared; mode 0 is treated as 1 (the pile needs the alignment), 2 adds the loci, which are not piled;
+ * scoring may be NULL, else as sw_batch_best_hits_local.  Everything *out answers is bit for bit what the same call without the pile
+ * answers. */
+int sw_batch_best_hits_pileup(const sw_batch *batch, const uint64_t *offsets, const char *blob, uint64_t n_queries, uint64_t k, uint64_t seed_copies,
+                              uint64_t mode, uint64_t min_seeds, const sw_scoring *scoring, const uint8_t *assembly_group, uint64_t n_groups,
+                              uint64_t max_dist_permille, sw_hits **out, sw_pileup **pile);
+/* Queries, bases of all queries (the table's rows), groups (any pointer may be NULL). */
+int sw_pileup_sizes(const sw_pileup *p, uint64_t *n_queries, uint64_t *total_bases, uint64_t *n_groups);
+/* D2H copy of the rows of queries [q0, q1): out[(bases of those queries) * n_groups * 8].  A range outside the queries -> SW_ERR_VALUE. */
+int sw_pileup_export(const sw_pileup *p, uint64_t q0, uint64_t q1, uint32_t *out);
+/* depth[n_queries * n_groups]. */
+int sw_pileup_depth(const sw_pileup *p, uint32_t *depth);
+/* counters[5] = { pairs piled, pairs filtered by distance, pairs left out by label, adds issued to the table, table bytes };
+ * ms[1] = { the pile walk } (HIP events, summed over rounds and chunks).  Either may be NULL. */
+int sw_pileup_stats(const sw_pileup *p, uint64_t *counters, double *ms);
+void sw_pileup_free(sw_pileup *p);
+
 /* ---- oligo search: every place where a primer or probe binds with at most d mismatches, on either strand (csrc/oligo.hip) ----
  * None of this has a counterpart in the reference.  It is NOT BLAST and NOT a thermodynamic model: no Tm, no dG, no e-values; one
  * exactly specified quantity, Hamming distance under IUPAC sets, over EVERY window of the resident batch -- no seed is needed, so no

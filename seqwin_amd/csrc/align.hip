@@ -277,6 +277,127 @@ __global__ __launch_bounds__(SQ_TPB) void k_al_walk(AlArgs a, uint64_t p0, uint6
     a.gaps[oi] = ng;
 }
 
+// The pile form of the walk: k_al_walk's rules on the same cells, the same four figures, and every column of
+// a piled pair added to the sink as it is decided.  The walk runs backwards: rules 1-3 consume pattern index r - 1, which is query
+// position r - 1 on strand 0 and m - r on strand 1; a run of rule 4 stays in a register and goes to its slot -- r on strand 0, m - r
+// on strand 1 -- when the next other op closes it.  Every add is an integer atomic whose result nobody reads.
+__device__ void pile_pair(const AlArgs &a, const PileSink &s, uint64_t i, unsigned long long *tally)
+{
+    const RunTable &t = a.t;
+    const sw_infix_pair p = a.pairs[i];
+    const uint32_t oi = a.out_idx ? a.out_idx[i] : (uint32_t)i;
+    const uint64_t qbase = a.qoff[p.query];
+    const uint32_t m = (uint32_t)(a.qoff[p.query + 1] - qbase), js = a.end[oi] - p.start;
+    const uint32_t strand = p.strand & 1u;
+    const uint32_t *codes = a.codes[strand], *valid = a.valid[strand];
+    const uint64_t tbase = t.rec_base[p.record] + p.start;
+    const uint32_t nb = (m + 63) >> 6;
+    uint32_t d = a.dist[oi];
+    // labels were checked on the host: below n_groups, or PILE_LEAVE_OUT
+    const uint32_t lab = s.group[s.group_mod ? oi % s.group_mod : oi];
+    const bool labelled = lab < s.n_groups, piled = labelled && (uint64_t)d * 1000 <= (uint64_t)s.max_dist_permille * m;
+    const uint64_t stride = (uint64_t)s.n_groups * PILE_CLASSES;
+    uint32_t *const rows = s.table + qbase * stride + (piled ? lab : 0u) * PILE_CLASSES;   // class c of position u: rows[u * stride + c]
+    Band band{};
+    if (m && js) band = band_of(m, js, d);
+    const uint64_t base = a.cell_off[i] - a.round_base;
+    RunMemo tm;
+    uint32_t ni = 0, nx = 0, ng = 0, r = m, j = js, run = 0, adds = 0;
+    uint64_t room = (uint64_t)m + d;   // ops a path of cost dist has at most
+    while (r > 0) {
+        if (room-- == 0) {
+            atomicOr(a.fail, 1u);
+            break;
+        }
+        uint32_t op = 2;   // column 0: D[r][0] = r, only rule 3 is left
+        uint32_t tcls = 4; // the class of text base j - 1 in the query's orientation
+        if (j > 0) {
+            const uint64_t qx = qbase + r - 1;
+            const bool pvalid = (valid[qx >> 5] >> (qx & 31)) & 1u;
+            const uint32_t pc = (uint32_t)load_codes(codes, qx, 1) & 3u;
+            const bool tvalid = valid32(t, p.record, p.start + j - 1, 1, tm) & 1u;
+            const uint32_t tc = (uint32_t)load_codes(t.packed, tbase + j - 1, 1) & 3u;
+            if (tvalid) tcls = strand ? 3u - tc : tc;
+            if (pvalid && tvalid && pc == tc) {
+                op = 0;
+            } else {
+                uint32_t diag;
+                if (r == 1) diag = 0;
+                else if (j == 1) diag = r - 1;
+                else {
+                    const uint32_t B = (r - 2) >> 6, bit = (r - 2) & 63u, ob = B == nb - 1 ? (m - 1) & 63u : 63u;
+                    const uint64_t slot = band_slot(band, B, j - 1);
+                    if (slot == ~0ull) {
+                        atomicOr(a.fail, 1u);
+                        break;
+                    }
+                    const uint64_t at = base + slot;
+                    const uint64_t below = (ob == 63 ? ~0ull : (1ull << (ob + 1)) - 1) & ~((2ull << bit) - 1);   // rows bit + 1 .. ob
+                    diag = a.sc[at] - (uint32_t)__popcll(a.pv[at] & below) + (uint32_t)__popcll(a.mv[at] & below);
+                }
+                if (diag + 1 == d) op = 1;
+                else {
+                    const uint64_t slot = band_slot(band, (r - 1) >> 6, j);
+                    if (slot == ~0ull) {
+                        atomicOr(a.fail, 1u);
+                        break;
+                    }
+                    const uint64_t at = base + slot;
+                    op = ((a.pv[at] >> ((r - 1) & 63u)) & 1ull) ? 2 : 3;
+                }
+            }
+        }
+        if (piled) {
+            if (op == 3) ++run;
+            else {
+                if (run) {
+                    // the run lies before pattern index r, which is neither 0 (the walk would have stopped) nor m (j* is the smallest
+                    // column of the minimum): its slot lies inside the query's rows
+                    if (r >= m) {
+                        atomicOr(a.fail, 1u);
+                        break;
+                    }
+                    uint32_t *const slot = rows + (uint64_t)(strand ? m - r : r) * stride;
+                    atomicAdd(slot + 6, 1u);
+                    atomicAdd(slot + 7, run);
+                    adds += 2;
+                    run = 0;
+                }
+                atomicAdd(rows + (uint64_t)(strand ? m - r : r - 1) * stride + (op == 2 ? 5u : tcls), 1u);
+                ++adds;
+            }
+        }
+        if (op == 0) ++ni;
+        else if (op == 1) ++nx;
+        else ++ng;
+        if (op != 0) --d;
+        if (op != 3) --r;
+        if (op != 2) --j;
+    }
+    if (run) atomicOr(a.fail, 1u);   // (a script does not begin with D)
+    a.a_start[oi] = p.start + j;
+    a.nident[oi] = ni;
+    a.mismatch[oi] = nx;
+    a.gaps[oi] = ng;
+    if (piled) {
+        atomicAdd(s.depth + (uint64_t)p.query * s.n_groups + lab, 1u);
+        atomicAdd(tally + PS_ADDS, (unsigned long long)adds);
+    }
+    atomicAdd(tally + (piled ? PS_PILED : labelled ? PS_FILTERED : PS_LEFT_OUT), 1ull);
+}
+
+// pairs [p0, p1) of the list, one lane each; the workgroup's counters go to the sink's in one add each
+__global__ __launch_bounds__(SQ_TPB) void k_al_walk_pile(AlArgs a, PileSink s, uint64_t p0, uint64_t p1)
+{
+    __shared__ unsigned long long tally[PS_N];
+    if (threadIdx.x < PS_N) tally[threadIdx.x] = 0;
+    __syncthreads();
+    const uint64_t i = p0 + (uint64_t)blockIdx.x * SQ_TPB + threadIdx.x;
+    if (i < p1) pile_pair(a, s, i, tally);
+    __syncthreads();
+    if (threadIdx.x < PS_N && tally[threadIdx.x]) atomicAdd(s.stat + threadIdx.x, tally[threadIdx.x]);
+}
+
 // script of pair x: ops [off[x], off[x + 1]) of the output, the last bytes of its padded slot
 __global__ __launch_bounds__(SQ_TPB) void k_al_compact(uint64_t b0, uint64_t total, const uint64_t *__restrict__ off, uint32_t n, const uint64_t *__restrict__ pad_end,
                                                        const uint8_t *__restrict__ padded, uint8_t *__restrict__ out)
@@ -294,7 +415,7 @@ __global__ __launch_bounds__(SQ_TPB) void k_al_compact(uint64_t b0, uint64_t tot
 }  // namespace
 
 void align_device(const Runs &runs, const QueryPack &P, const sw_infix_pair *d_pairs, const uint32_t *d_out_idx, uint64_t n, const uint32_t *d_dist,
-                  const uint32_t *d_end, uint32_t *const out[4], uint8_t *d_ops, const uint64_t *d_ops_end, AlignStats &st)
+                  const uint32_t *d_end, uint32_t *const out[4], uint8_t *d_ops, const uint64_t *d_ops_end, AlignStats &st, const PileSink *pile)
 {
     if (!n) return;
     if (n > SQ_MAX_LIST) raise(SW_ERR_VALUE, "infix alignments: %llu pairs exceed one launch of the list kernels (%llu)", (unsigned long long)n, (unsigned long long)SQ_MAX_LIST);
@@ -420,7 +541,8 @@ void align_device(const Runs &runs, const QueryPack &P, const sw_infix_pair *d_p
         SW_HIP(hipEventRecord(e1, stream));
         for (uint64_t x0 = p0; x0 < p1; x0 += max_threads) {
             const uint64_t x1 = std::min<uint64_t>(p1, x0 + max_threads);
-            hipLaunchKernelGGL(k_al_walk, dim3(sq_blocks(x1 - x0)), dim3(SQ_TPB), 0, stream, a, x0, x1);
+            if (pile) hipLaunchKernelGGL(k_al_walk_pile, dim3(sq_blocks(x1 - x0)), dim3(SQ_TPB), 0, stream, a, *pile, x0, x1);
+            else hipLaunchKernelGGL(k_al_walk, dim3(sq_blocks(x1 - x0)), dim3(SQ_TPB), 0, stream, a, x0, x1);
             SW_HIP(hipGetLastError());
         }
         SW_HIP(hipEventRecord(e2, stream));
@@ -441,6 +563,59 @@ void align_device(const Runs &runs, const QueryPack &P, const sw_infix_pair *d_p
     st.counters[4] = std::max(st.counters[4], peak_cells * ALN_CELL_BYTES);
     st.counters[6] = std::max(st.counters[6], largest * ALN_CELL_BYTES);
     st.counters[7] += launches;
+}
+
+// ---- the pileup's tables ---------------------------------------------------------------------------------
+// n_piles: the pairs of the call or the assemblies of the batch -- the most one counter can be added to
+void check_pile_args(const char *what, uint64_t n_groups, uint64_t max_dist_permille, const uint8_t *labels, uint64_t n_labels, uint64_t n_piles,
+                     const uint64_t *offsets, uint64_t nq)
+{
+    if (n_groups < 1 || n_groups > 8) raise(SW_ERR_VALUE, "%s: the pileup takes 1..8 groups (got %llu)", what, (unsigned long long)n_groups);
+    if (max_dist_permille > 1000) raise(SW_ERR_VALUE, "%s: max_dist_permille must lie in 0..1000 (got %llu)", what, (unsigned long long)max_dist_permille);
+    if (n_labels && !labels) raise(SW_ERR_VALUE, "%s: a NULL handle or array", what);
+    for (uint64_t i = 0; i < n_labels; ++i)
+        if (labels[i] >= n_groups && labels[i] != PILE_LEAVE_OUT)
+            raise(SW_ERR_VALUE, "%s: group label %u at %llu is neither below the %llu groups nor 255 (leave out)", what, (unsigned)labels[i], (unsigned long long)i,
+                  (unsigned long long)n_groups);
+    uint64_t max_q = 0;
+    for (uint64_t q = 0; q < nq; ++q) max_q = std::max(max_q, offsets[q + 1] - offsets[q]);
+    if (n_piles && max_q && (n_piles >= (1ull << 32) || max_q >= (1ull << 32) || n_piles * max_q >= (1ull << 32)))
+        raise(SW_ERR_VALUE, "%s: %llu pairs or assemblies times the longest query (%llu) do not fit the pileup's 32-bit counters", what,
+              (unsigned long long)n_piles, (unsigned long long)max_q);
+}
+
+void pile_begin(sw_pileup &p, int device, const uint64_t *offsets, uint64_t nq, uint64_t n_groups, uint64_t max_dist_permille, const uint8_t *labels,
+                uint64_t n_labels, uint64_t group_mod)
+{
+    const hipStream_t stream = HIT_STREAM;
+    p.device = device;
+    p.nq = nq;
+    p.n_groups = n_groups;
+    p.off.assign(offsets, offsets + nq + 1);
+    const uint64_t cells = p.off[nq] * n_groups * PILE_CLASSES;
+    p.table.alloc(cells);
+    p.depth.alloc(nq * n_groups);
+    p.labels.alloc(n_labels);
+    p.stat.alloc(PS_N);
+    if (cells) SW_HIP(hipMemsetAsync(p.table.p, 0, cells * 4, stream));
+    if (nq) SW_HIP(hipMemsetAsync(p.depth.p, 0, nq * n_groups * 4, stream));
+    SW_HIP(hipMemsetAsync(p.stat.p, 0, PS_N * sizeof(unsigned long long), stream));
+    if (n_labels) SW_HIP(hipMemcpyAsync(p.labels.p, labels, n_labels, hipMemcpyHostToDevice, stream));
+    SW_HIP(hipStreamSynchronize(stream));   // (the labels are the caller's)
+    p.sink = PileSink{p.table.p, p.depth.p, p.labels.p, group_mod, (uint32_t)n_groups, (uint32_t)max_dist_permille, p.stat.p};
+    p.counters[4] = cells * 4;
+}
+
+void pile_finish(sw_pileup &p, double walk_ms)
+{
+    unsigned long long st[PS_N] = {};
+    SW_HIP(hipMemcpyAsync(st, p.stat.p, sizeof st, hipMemcpyDeviceToHost, HIT_STREAM));
+    SW_HIP(hipStreamSynchronize(HIT_STREAM));
+    for (int x = 0; x < PS_N; ++x) p.counters[x] = st[x];
+    p.ms = walk_ms;
+    p.labels.release();
+    p.stat.release();
+    p.sink = PileSink{};
 }
 
 }  // namespace sw
@@ -549,6 +724,105 @@ int sw_ops_export(const sw_ops *o, uint64_t *offsets, uint8_t *ops)
 void sw_ops_free(sw_ops *o)
 {
     delete o;
+}
+
+int sw_batch_infix_pileup(const sw_batch *b, const uint64_t *offsets, const char *blob, uint64_t n_queries, const sw_infix_pair *pairs, uint64_t n,
+                          const uint8_t *pair_group, uint64_t n_groups, uint64_t max_dist_permille, uint32_t *dist, uint32_t *end, uint32_t *a_start,
+                          uint32_t *nident, uint32_t *mismatch, uint32_t *gaps, sw_pileup **out, uint64_t *counters, double *ms)
+{
+    return guarded([&] {
+        const char *what = "infix pileup";
+        check_queries(what, offsets, blob, n_queries);
+        check_pile_args(what, n_groups, max_dist_permille, pair_group, n, n, offsets, n_queries);
+        if (!out) raise(SW_ERR_VALUE, "%s: a NULL handle or array", what);
+        check_infix_pairs(what, b, offsets, blob, n_queries, pairs, n, dist && end && a_start && nident && mismatch && gaps);
+        StreamScope scope(HIT_STREAM);
+        DevRuns runs(*b);
+        const uint64_t total = n_queries ? offsets[n_queries] : 0;
+        DevArray<uint8_t> text(total);
+        if (total) SW_HIP(hipMemcpyAsync(text.p, blob, total, hipMemcpyHostToDevice, HIT_STREAM));
+        QueryPack P;
+        pack_queries(text.p, offsets, n_queries, P);
+        DevArray<sw_infix_pair> d_pairs(n);
+        DevArray<uint32_t> d_dist(n), d_end(n), d_out[4];
+        for (auto &o : d_out) o.alloc(n);
+        if (n) SW_HIP(hipMemcpyAsync(d_pairs.p, pairs, n * sizeof(sw_infix_pair), hipMemcpyHostToDevice, HIT_STREAM));
+        double dms[1] = {};
+        infix_device(runs_of(runs.t), P, d_pairs.p, nullptr, n, d_dist.p, d_end.p, nullptr, dms);
+        const uint64_t no_query[1] = {0};
+        std::unique_ptr<sw_pileup> p(new sw_pileup);
+        pile_begin(*p, b->device, n_queries ? offsets : no_query, n_queries, n_groups, max_dist_permille, pair_group, n, 0);
+        AlignStats st;
+        uint32_t *const dev[4] = {d_out[0].p, d_out[1].p, d_out[2].p, d_out[3].p};
+        align_device(runs_of(runs.t), P, d_pairs.p, nullptr, n, d_dist.p, d_end.p, dev, nullptr, nullptr, st, &p->sink);
+        pile_finish(*p, st.ms[1]);
+        uint32_t *const host[6] = {dist, end, a_start, nident, mismatch, gaps};
+        const uint32_t *const from[6] = {d_dist.p, d_end.p, d_out[0].p, d_out[1].p, d_out[2].p, d_out[3].p};
+        if (n)
+            for (int f = 0; f < 6; ++f) SW_HIP(hipMemcpy(host[f], from[f], n * 4, hipMemcpyDeviceToHost));
+        if (counters) memcpy(counters, st.counters, sizeof st.counters);
+        if (ms) {
+            ms[0] = dms[0];
+            ms[1] = st.ms[0];
+            ms[2] = st.ms[1];
+        }
+        *out = p.release();
+    });
+}
+
+static const sw_pileup &pile_of(const sw_pileup *p)
+{
+    if (!p) raise(SW_ERR_VALUE, "pileup: a NULL handle");
+    return *p;
+}
+
+int sw_pileup_sizes(const sw_pileup *p, uint64_t *n_queries, uint64_t *total_bases, uint64_t *n_groups)
+{
+    return guarded([&] {
+        const sw_pileup &x = pile_of(p);
+        if (n_queries) *n_queries = x.nq;
+        if (total_bases) *total_bases = x.off[x.nq];
+        if (n_groups) *n_groups = x.n_groups;
+    });
+}
+
+int sw_pileup_export(const sw_pileup *p, uint64_t q0, uint64_t q1, uint32_t *out)
+{
+    return guarded([&] {
+        const sw_pileup &x = pile_of(p);
+        if (q0 > q1 || q1 > x.nq)
+            raise(SW_ERR_VALUE, "pileup: queries [%llu, %llu) lie outside the %llu queries", (unsigned long long)q0, (unsigned long long)q1, (unsigned long long)x.nq);
+        const uint64_t per = x.n_groups * PILE_CLASSES, cells = (x.off[q1] - x.off[q0]) * per;
+        if (!cells) return;
+        if (!out) raise(SW_ERR_VALUE, "pileup: a NULL handle or array");
+        require_device(x.device, "the pileup");
+        SW_HIP(hipMemcpy(out, x.table.p + x.off[q0] * per, cells * 4, hipMemcpyDeviceToHost));
+    });
+}
+
+int sw_pileup_depth(const sw_pileup *p, uint32_t *depth)
+{
+    return guarded([&] {
+        const sw_pileup &x = pile_of(p);
+        if (!x.nq) return;
+        if (!depth) raise(SW_ERR_VALUE, "pileup: a NULL handle or array");
+        require_device(x.device, "the pileup");
+        SW_HIP(hipMemcpy(depth, x.depth.p, x.nq * x.n_groups * 4, hipMemcpyDeviceToHost));
+    });
+}
+
+int sw_pileup_stats(const sw_pileup *p, uint64_t *counters, double *ms)
+{
+    return guarded([&] {
+        const sw_pileup &x = pile_of(p);
+        if (counters) memcpy(counters, x.counters, sizeof x.counters);
+        if (ms) ms[0] = x.ms;
+    });
+}
+
+void sw_pileup_free(sw_pileup *p)
+{
+    delete p;
 }
 
 int sw_hits_align_block(const sw_hits *h, uint64_t field, uint64_t r0, uint64_t r1, uint64_t c0, uint64_t c1, uint32_t *out)

@@ -870,8 +870,16 @@ namespace {
 // lists, k_hit_probe_shared).  Everything behind the probe is the same code for both
 // local != nullptr: the local alignment (local.hip) of the winners' pairs, and in loci mode of the loci's,
 // right behind their distances; nullptr: not one pass more than before
+// pile != nullptr (it needs align): the winners' traceback also adds every piled winner to the pileup's tables (align.hip, DESIGN.md
+// section 3.2k), labelled by its assembly; the loci's traceback stays the plain one
+struct PileCall {
+    sw_pileup *p;
+    const uint8_t *assembly_group;
+    uint64_t n_groups, max_dist_permille;
+};
+
 void batch_best_hits(const sw_batch &b, const uint64_t *offsets, const char *blob, uint64_t nq, uint32_t k, bool align, uint64_t min_seeds, uint32_t seed_copies,
-                     const sw_scoring *local, sw_hits &o)
+                     const sw_scoring *local, sw_hits &o, const PileCall *pile = nullptr)
 {
     const bool loci = min_seeds > 0;
     std::vector<LociChunk> loci_chunks;
@@ -895,6 +903,10 @@ void batch_best_hits(const sw_batch &b, const uint64_t *offsets, const char *blo
             o.afield[f].alloc(n_cells);
             if (n_cells) SW_HIP(hipMemsetAsync(o.afield[f].p, 0xFF, n_cells * 4, stream));
         }
+    if (pile) {
+        const uint64_t no_query[1] = {0};
+        pile_begin(*pile->p, b.device, nq ? offsets : no_query, nq, pile->n_groups, pile->max_dist_permille, pile->assembly_group, n_asm, n_asm);
+    }
     o.has_local = local != nullptr;
     if (local)
         for (uint32_t f = 0; f < LOCAL_FIELDS; ++f) {
@@ -1106,7 +1118,8 @@ void batch_best_hits(const sw_batch &b, const uint64_t *offsets, const char *blo
                 o.ms[3] += dms[0];
                 if (align) {
                     uint32_t *const out[4] = {o.afield[0].p, o.afield[1].p, o.afield[2].p, o.afield[3].p};
-                    align_device(runs_of(runs.t), P, pairs.p, out_idx.p, n_pairs, o.field[4].p, o.field[3].p, out, nullptr, nullptr, o.align);
+                    align_device(runs_of(runs.t), P, pairs.p, out_idx.p, n_pairs, o.field[4].p, o.field[3].p, out, nullptr, nullptr, o.align,
+                                 pile ? &pile->p->sink : nullptr);
                 }
                 if (local) {
                     uint32_t *lout[LOCAL_FIELDS];
@@ -1153,6 +1166,7 @@ void batch_best_hits(const sw_batch &b, const uint64_t *offsets, const char *blo
         }
     }
     SW_HIP(hipStreamSynchronize(stream));
+    if (pile) pile_finish(*pile->p, o.align.ms[1]);
     if (loci) {
         Event f0, f1;
         SW_HIP(hipEventRecord(f0, stream));
@@ -1196,7 +1210,7 @@ namespace {
 
 // min_seeds: nullptr without the loci mode; seed_copies: nullptr for the unique-seed route
 void best_hits_entry(const sw_batch *batch, const uint64_t *offsets, const char *blob, uint64_t n_queries, uint64_t k, bool align, const uint64_t *min_seeds,
-                     sw_hits **out, const uint64_t *seed_copies = nullptr, const sw_scoring *local = nullptr)
+                     sw_hits **out, const uint64_t *seed_copies = nullptr, const sw_scoring *local = nullptr, PileCall *pile = nullptr, sw_pileup **pile_out = nullptr)
 {
     if (k < 1 || k > 32) raise(SW_ERR_VALUE, "best hits: k-mer length must lie in 1..32 (got %llu)", (unsigned long long)k);
     if (seed_copies && (*seed_copies < 1 || *seed_copies > 256))
@@ -1209,13 +1223,21 @@ void best_hits_entry(const sw_batch *batch, const uint64_t *offsets, const char 
             if (offsets[q + 1] - offsets[q] > 65279)
                 raise(SW_ERR_VALUE, "best hits: query %llu has %llu bases, above the 65279 the local alignment takes", (unsigned long long)q,
                       (unsigned long long)(offsets[q + 1] - offsets[q]));
+    if (pile) {
+        if (!pile_out) raise(SW_ERR_VALUE, "best hits: a NULL handle or array");
+        check_pile_args("best hits", pile->n_groups, pile->max_dist_permille, pile->assembly_group, batch->host.n_assemblies, batch->host.n_assemblies, offsets,
+                        n_queries);
+    }
     if (batch->host.rec_len.size() && !batch->d_packed.p) raise(SW_ERR_VALUE, "best hits: the batch holds no packed bases (it must be resident)");
     require_device(batch->device, "the batch");
     StreamScope scope(HIT_STREAM);
     std::unique_ptr<sw_hits> o(new sw_hits);
+    std::unique_ptr<sw_pileup> po(pile ? new sw_pileup : nullptr);
+    if (pile) pile->p = po.get();
     o->device = batch->device;
-    batch_best_hits(*batch, offsets, blob, n_queries, (uint32_t)k, align, min_seeds ? *min_seeds : 0, seed_copies ? (uint32_t)*seed_copies : 0u, local, *o);
+    batch_best_hits(*batch, offsets, blob, n_queries, (uint32_t)k, align, min_seeds ? *min_seeds : 0, seed_copies ? (uint32_t)*seed_copies : 0u, local, *o, pile);
     *out = o.release();
+    if (pile) *pile_out = po.release();
 }
 
 }  // namespace
@@ -1279,6 +1301,20 @@ int sw_batch_best_hits_local(const sw_batch *batch, const uint64_t *offsets, con
         if (mode > 2) raise(SW_ERR_VALUE, "best hits: mode %llu is none of plain, aligned, loci (0..2)", (unsigned long long)mode);
         check_scoring("best hits", scoring);
         best_hits_entry(batch, offsets, blob, n_queries, k, mode >= 1, mode == 2 ? &min_seeds : nullptr, out, seed_copies ? &seed_copies : nullptr, scoring);
+    });
+}
+
+int sw_batch_best_hits_pileup(const sw_batch *batch, const uint64_t *offsets, const char *blob, uint64_t n_queries, uint64_t k, uint64_t seed_copies,
+                              uint64_t mode, uint64_t min_seeds, const sw_scoring *scoring, const uint8_t *assembly_group, uint64_t n_groups,
+                              uint64_t max_dist_permille, sw_hits **out, sw_pileup **pile)
+{
+    return guarded([&] {
+        if (mode > 2) raise(SW_ERR_VALUE, "best hits: mode %llu is none of plain, aligned, loci (0..2)", (unsigned long long)mode);
+        if (scoring) check_scoring("best hits", scoring);
+        // (the counts of groups and the bound say what they say without the batch; the labels are checked once its assemblies are known)
+        check_pile_args("best hits", n_groups, max_dist_permille, nullptr, 0, 0, nullptr, 0);
+        PileCall pc{nullptr, assembly_group, n_groups, max_dist_permille};
+        best_hits_entry(batch, offsets, blob, n_queries, k, true, mode == 2 ? &min_seeds : nullptr, out, seed_copies ? &seed_copies : nullptr, scoring, &pc, pile);
     });
 }
 

@@ -45,6 +45,20 @@ struct HitLoci {
     double ms[4] = {};
 };
 
+// The pileup's sink of a traceback (align.hip): where the pile walk adds what it sees.  The label of the pair
+// with out index x is group[x] (group_mod == 0: a label per pair) or group[x % group_mod] (a label per assembly of a hits matrix).
+constexpr uint32_t PILE_CLASSES = 8;   // A, C, G, T, N, DEL, INS, INS_BASES
+constexpr uint8_t PILE_LEAVE_OUT = 0xFF;
+enum { PS_PILED, PS_FILTERED, PS_LEFT_OUT, PS_ADDS, PS_N };
+struct PileSink {
+    uint32_t *table;             // [total query bases][n_groups][PILE_CLASSES]
+    uint32_t *depth;             // [nq][n_groups]
+    const uint8_t *group;
+    uint64_t group_mod;
+    uint32_t n_groups, max_dist_permille;
+    unsigned long long *stat;    // [PS_N]
+};
+
 // RunTable (seqs_core.hpp) has internal linkage like every type of that header; this is the same table as the two files hand it to
 // each other (runs_of / table_of below)
 struct Runs {
@@ -64,8 +78,17 @@ void check_infix_pairs(const char *what, const sw_batch *b, const uint64_t *offs
 // align.hip: the canonical traceback of n valid pairs (device list) whose Layer A results lie at d_dist / d_end [out index of the
 // pair].  out[4] = a_start, nident, mismatch, gaps at the same index.  d_ops != nullptr: pair i's script is written so that it ends
 // at d_ops[d_ops_end[i]] (exclusive), the slot in front of it holding |query| + dist bytes.  st is added to.
+// pile != nullptr: the pile walk stands in for the plain walk -- the same four figures, and every piled pair's columns added to the
+// sink; nullptr: not one kernel or argument differs from a call made before the pileup existed.
 void align_device(const Runs &t, const QueryPack &P, const sw_infix_pair *d_pairs, const uint32_t *d_out_idx, uint64_t n, const uint32_t *d_dist,
-                  const uint32_t *d_end, uint32_t *const out[4], uint8_t *d_ops, const uint64_t *d_ops_end, AlignStats &st);
+                  const uint32_t *d_end, uint32_t *const out[4], uint8_t *d_ops, const uint64_t *d_ops_end, AlignStats &st,
+                  const PileSink *pile = nullptr);
+// align.hip: the pileup's argument checks (before a device is touched), its zeroed tables, the sink that adds to them, its counters
+void check_pile_args(const char *what, uint64_t n_groups, uint64_t max_dist_permille, const uint8_t *labels, uint64_t n_labels, uint64_t n_piles,
+                     const uint64_t *offsets, uint64_t nq);
+void pile_begin(sw_pileup &p, int device, const uint64_t *offsets, uint64_t nq, uint64_t n_groups, uint64_t max_dist_permille, const uint8_t *labels,
+                uint64_t n_labels, uint64_t group_mod);
+void pile_finish(sw_pileup &p, double walk_ms);
 
 // local.hip: the nine figures of n valid pairs (device list) under scoring system sc, written at the pair's out index; every side
 // of a pair is below 2^16 (the callers check it on the host).  st is added to.
@@ -93,6 +116,18 @@ __device__ __forceinline__ uint32_t plane32(const uint32_t *__restrict__ valid, 
 
 }  // namespace
 }  // namespace sw
+
+struct sw_pileup {
+    int device = 0;
+    uint64_t nq = 0, n_groups = 0;
+    std::vector<uint64_t> off;                     // [nq + 1]: the rows of query q are [off[q], off[q + 1])
+    sw::DevArray<uint32_t> table, depth;
+    sw::DevArray<uint8_t> labels;
+    sw::DevArray<unsigned long long> stat;
+    sw::PileSink sink{};
+    uint64_t counters[5] = {};                     // pairs piled, filtered by distance, left out by label, adds issued, table bytes
+    double ms = 0;                                 // the pile walk
+};
 
 struct sw_hits {
     int device = 0;

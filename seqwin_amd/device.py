@@ -184,6 +184,22 @@ class Batch:
             res += (d,)
         return res
 
+    def infix_pileup(self, queries, pairs, groups, n_groups=None, max_dist_permille: int = 1000):
+        """``(Pileup, (dist, end, start, nident, mismatch, gaps))``: :meth:`infix_alignments` whose walk also counts, per query
+        position and group, what the pairs' canonical alignments put there (csrc/align.hip).  ``groups`` is
+        one label per pair: 0 .. ``n_groups - 1`` (``n_groups`` in 1..8; None: the largest label + 1), or 255 to leave the pair out.
+        A pair is piled iff ``dist * 1000 <= max_dist_permille * len(query)``; the default piles every labelled pair.  The counts
+        are exact and do not depend on the order of the pairs.  Not BLAST, and not a multiple alignment: every pair is aligned to
+        its query alone.  ValueError for a label in ``n_groups..254``, ``n_groups`` outside 1..8 or a bound outside 0..1000."""
+        offs, blob, nq = _query_csr(queries)
+        pr = _infix_pairs(pairs)
+        lab, ng = _pile_groups(groups, len(pr), n_groups, "pair")
+        out = [np.empty(len(pr), np.uint32) for _ in range(6)]
+        h = c_vp()
+        check(lib.sw_batch_infix_pileup(self._h, _ptr(offs), blob, c_u64(nq), _ptr(pr), c_u64(len(pr)), _ptr(lab), c_u64(ng), c_u64(int(max_dist_permille)),
+                                        *[_ptr(a) for a in out], ctypes.byref(h), None, None))
+        return Pileup(h, offs), tuple(out)
+
     def local_alignments(self, queries, pairs, scoring=(2, -3, 5, 2), stats: bool = False) -> dict:
         """The optimal LOCAL alignment of every pair of :meth:`infix_distances` under the scoring system ``(reward, penalty, gapopen,
         gapextend)`` -- a gap of L columns costs ``gapopen + L * gapextend``; the default is blastn's (csrc/local.hip, DESIGN.md section
@@ -205,7 +221,7 @@ class Batch:
         return res
 
     def best_hits(self, queries, kmerlen: int, align: bool = False, loci: bool = False, min_seeds: int = 1, seed_copies=None, local: bool = False,
-                  scoring=(2, -3, 5, 2)) -> "BestHits":
+                  scoring=(2, -3, 5, 2), pileup=None, n_groups=None, max_dist_permille: int = 1000) -> "BestHits":
         """For every query (a list of ``str`` or ``bytes``) and every assembly: the best seeded locus and the exact infix edit
         distance of the query to the best substring there (csrc/hits.hip).  A seed is a canonical
         ``kmerlen``-mer that exactly one window of ALL the query text has and that is not its own reverse complement: a query whose
@@ -230,11 +246,24 @@ class Batch:
         ``qstart()``, ``qend()``, ``sstart()``, ``send()``, ``local_nident()``, ``local_mismatch()``, ``local_gapopen()``,
         ``local_gaps()`` and ``local_stats()``, and with ``loci=True`` its ``loci()`` has nine ``local_*`` columns.  A copy of which
         an assembly holds only a part reads as a large ``dist`` and as a clean local hit over that part.  Still not BLAST: our seeds and
-        windows, no X-drop, no e-values.  ValueError for a query above 65279 bases."""
+        windows, no X-drop, no e-values.  ValueError for a query above 65279 bases.
+        ``pileup=groups`` (it implies ``align=True``, combines with everything above and changes none of it)
+        piles every winner's canonical alignment into the group of its assembly -- one label per assembly, 0 .. ``n_groups - 1`` or 255
+        to leave the assembly out, ``n_groups`` and ``max_dist_permille`` as :meth:`infix_pileup` takes them: the result then answers
+        ``pileup()``, a :class:`Pileup` of base counts per query position and group.  The loci of ``loci=True`` are not piled."""
         offs, blob, nq = _query_csr(queries)
         h = c_vp()
         if loci and int(min_seeds) < 1:
             raise ValueError(f"min_seeds must be at least 1 (got {min_seeds})")
+        if pileup is not None:
+            if seed_copies is not None and not 1 <= int(seed_copies) <= 256:
+                raise ValueError(f"seed_copies must lie in 1..256 (got {seed_copies})")
+            lab, ng = _pile_groups(pileup, self.info()["n_assemblies"], n_groups, "assembly")
+            ph = c_vp()
+            check(lib.sw_batch_best_hits_pileup(self._h, _ptr(offs), blob, c_u64(nq), c_u64(int(kmerlen)), c_u64(int(seed_copies or 0)), c_u64(2 if loci else 1),
+                                                c_u64(int(min_seeds) if loci else 0), _scoring(scoring) if local else None, _ptr(lab), c_u64(ng),
+                                                c_u64(int(max_dist_permille)), ctypes.byref(h), ctypes.byref(ph)))
+            return BestHits(h, aligned=True, loci=bool(loci), local=bool(local), pileup=Pileup(ph, offs))
         if local:
             if seed_copies is not None and not 1 <= int(seed_copies) <= 256:
                 raise ValueError(f"seed_copies must lie in 1..256 (got {seed_copies})")
@@ -324,6 +353,26 @@ def _query_csr(queries):
     offs = np.zeros(len(qs) + 1, np.uint64)
     np.cumsum([len(q) for q in qs], out=offs[1:])
     return offs, b"".join(qs), len(qs)
+
+
+PILE_CLASSES = ("A", "C", "G", "T", "N", "DEL", "INS", "INS_BASES")   # the last axis of a pileup's table
+PILE_LEAVE_OUT = 0xFF   # the group label that keeps a pair or an assembly out of the pileup
+
+
+def _pile_groups(groups, n: int, n_groups, what: str):
+    """(labels uint8[n], n_groups) of a pileup call; the library checks the labels against ``n_groups``."""
+    a = np.asarray(groups)
+    if a.ndim != 1 or len(a) != n:
+        raise ValueError(f"the pileup takes one group label per {what}: {n} (got an array of shape {a.shape})")
+    if a.dtype == np.bool_ or not (np.issubdtype(a.dtype, np.integer) or not len(a)):
+        raise ValueError(f"group labels are integers 0..7 or {PILE_LEAVE_OUT} (got {a.dtype})")
+    a = a.astype(np.int64)
+    if len(a) and (a.min() < 0 or a.max() > 0xFF):
+        raise ValueError(f"group labels are integers 0..7 or {PILE_LEAVE_OUT}")
+    if n_groups is None:
+        kept = a[a != PILE_LEAVE_OUT]
+        n_groups = int(kept.max()) + 1 if len(kept) else 1
+    return np.ascontiguousarray(a.astype(np.uint8)), int(n_groups)
 
 
 LOCAL_FIELDS = ("score", "qstart", "qend", "sstart", "send", "nident", "mismatch", "gapopen", "gaps")
@@ -727,16 +776,19 @@ class Markers:
         return batch.screen([blob[o[i]:o[i + 1]] for i in range(len(o) - 1)], kmerlen)
 
     def best_hits(self, batch: "Batch", kmerlen: int, select=None, align: bool = False, loci: bool = False, min_seeds: int = 1,
-                  seed_copies=None, local: bool = False, scoring=(2, -3, 5, 2)) -> "BestHits":
+                  seed_copies=None, local: bool = False, scoring=(2, -3, 5, 2), pileup=None, n_groups=None, max_dist_permille: int = 1000) -> "BestHits":
         """:meth:`Batch.best_hits` of the representatives' text -- ``sequences(batch, "reps", select)``, in that order -- against
         every assembly of ``batch``.  ``kmerlen`` is the caller's choice; it need not be the graph's k.  ``seed_copies`` is that
         call's: ``None`` keeps a k-mer as a seed only if one window of all representatives has it, ``c`` in 1..256 lets up to c
         windows share it (representatives that overlap or repeat keep their k-mers) and drops a k-mer with more windows whole.
-        ``local`` and ``scoring`` are that call's too: the local alignment of every winner (and locus) with affine gap scores."""
+        ``local`` and ``scoring`` are that call's too: the local alignment of every winner (and locus) with affine gap scores; so
+        are ``pileup``, ``n_groups`` and ``max_dist_permille``: the winners' base counts per position of every representative, by
+        group of assembly."""
         offs, blob, _ = self.sequences(batch, "reps", select)
         o = offs.astype(np.int64)
         return batch.best_hits([blob[o[i]:o[i + 1]] for i in range(len(o) - 1)], kmerlen, align=align, loci=loci, min_seeds=min_seeds,
-                               seed_copies=seed_copies, local=local, scoring=scoring)
+                               seed_copies=seed_copies, local=local, scoring=scoring, pileup=pileup, n_groups=n_groups,
+                               max_dist_permille=max_dist_permille)
 
     def candidates(self, min_len: int) -> np.ndarray:
         """Indices of the subgraphs the reference keeps (markers.py:514-517): len >= min_len, neither single nor dup."""
@@ -1039,6 +1091,67 @@ class OligoHits:
 LOCI_FIELDS = ("query", "assembly", "record", "strand", "band", "seeds", "dist", "end", "start", "nident", "mismatch", "gaps", "dup")
 
 
+class Pileup:
+    """Base counts per query position and group over the canonical alignments of a call's pairs, resident on the device
+    (:meth:`Batch.infix_pileup`, ``Batch.best_hits(pileup=...)``; csrc/align.hip).  The last axis is
+    PILE_CLASSES: the text bases ``A``, ``C``, ``G``, ``T`` facing the position (in the query's orientation), ``N`` for an invalid text
+    base, ``DEL`` for a gap facing it; ``INS`` counts the insertions between positions u - 1 and u, ``INS_BASES`` their bases.  Exact
+    integers; the first six add up to the depth at every position.  Not BLAST and not a multiple alignment."""
+
+    def __init__(self, handle: c_vp, offsets: np.ndarray):
+        self._h = handle
+        self._offs = np.array(offsets, np.uint64)
+
+    def sizes(self):
+        """(queries, bases of all queries, groups)"""
+        v = [c_u64() for _ in range(3)]
+        check(lib.sw_pileup_sizes(self._h, *[ctypes.byref(x) for x in v]))
+        return tuple(x.value for x in v)
+
+    def _rows(self, q0: int, q1: int) -> np.ndarray:
+        ng = self.sizes()[2]
+        out = np.empty((int(self._offs[q1] - self._offs[q0]), ng, len(PILE_CLASSES)), np.uint32)
+        check(lib.sw_pileup_export(self._h, c_u64(q0), c_u64(q1), _ptr(out) if out.size else None))
+        return out
+
+    def counts(self, q: int) -> np.ndarray:
+        """uint32[len(query q), groups, 8]"""
+        q = int(q)
+        if not 0 <= q < len(self._offs) - 1:
+            raise ValueError(f"query {q} is none of the call's {len(self._offs) - 1}")
+        return self._rows(q, q + 1)
+
+    def table(self):
+        """``(offsets, uint32[total, groups, 8])``: the rows of query q are ``[offsets[q], offsets[q + 1])``."""
+        return self._offs.copy(), self._rows(0, len(self._offs) - 1)
+
+    def depth(self) -> np.ndarray:
+        """uint32[queries, groups]: the pairs of every query piled into every group."""
+        nq, _, ng = self.sizes()
+        out = np.empty((nq, ng), np.uint32)
+        check(lib.sw_pileup_depth(self._h, _ptr(out) if out.size else None))
+        return out
+
+    def stats(self) -> dict:
+        c = (c_u64 * 5)()
+        ms = (ctypes.c_double * 1)()
+        check(lib.sw_pileup_stats(self._h, c, ms))
+        d = dict(zip(("piled", "filtered_by_distance", "left_out_by_label", "adds", "table_bytes"), (int(x) for x in c)))
+        d.update(pile_walk_ms=ms[0])
+        return d
+
+    def close(self) -> None:
+        if self._h:
+            lib.sw_pileup_free(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class BestHits:
     """The best hit of every query in every assembly of a batch, resident on the device (:meth:`Batch.best_hits`,
     :meth:`Markers.best_hits`; csrc/hits.hip): per (query, assembly) the winning locus' vote ``seeds``, its
@@ -1052,13 +1165,21 @@ class BestHits:
     ``sum_nident`` over the loci that are no duplicates -- counts, 0 where there is none.  Made with ``local=True`` it also holds the
     optimal local alignment of every hit on its window under an affine scoring system (csrc/local.hip; still
     not BLAST): ``score``, ``qstart``, ``qend``, ``sstart``, ``send``, ``local_nident``, ``local_mismatch``, ``local_gapopen`` and
-    ``local_gaps``, NO_HIT where there is no hit."""
+    ``local_gaps``, NO_HIT where there is no hit.  Made with ``pileup=groups`` it also holds the :class:`Pileup` of the winners'
+    canonical alignments by group of assembly: ``pileup()``."""
 
-    def __init__(self, handle: c_vp, aligned: bool = False, loci: bool = False, local: bool = False):
+    def __init__(self, handle: c_vp, aligned: bool = False, loci: bool = False, local: bool = False, pileup: "Pileup | None" = None):
         self._h = handle
         self._aligned = aligned
         self._loci = loci
         self._local = local
+        self._pileup = pileup
+
+    def pileup(self) -> "Pileup":
+        """The :class:`Pileup` of the winners; it is closed with these hits."""
+        if self._pileup is None:
+            raise ValueError("these best hits were made without pileup=groups")
+        return self._pileup
 
     def sizes(self):
         """(queries, assemblies, seeds of all queries, k)"""
@@ -1270,6 +1391,8 @@ class BestHits:
                          "hits"), (int(x) for x in c)))
 
     def close(self) -> None:
+        if self._pileup is not None:
+            self._pileup.close()
         if self._h:
             lib.sw_hits_free(self._h)
             self._h = None

@@ -1,0 +1,37 @@
+"""The pileup on the RELEASE library (seqwin_amd/libseqwin_hip.so: test hooks compiled out): the tests of
+tests/test_gpu_pileup_direct.py and tests/test_gpu_best_hits_pileup.py that need no hook, in a fresh interpreter with
+SEQWIN_AMD_RELEASE_LIB=1 (the pattern of tests/test_release_library_align.py)."""
+import os
+import subprocess
+import sys
+from pathlib import Path
+
+import pytest
+
+ROOT = Path(__file__).resolve().parent.parent
+
+
+def test_both_libraries_export_the_pileup():
+    rel, tst = ROOT / "seqwin_amd" / "libseqwin_hip.so", ROOT / "seqwin_amd" / "libseqwin_hip_test.so"
+    assert rel.exists() and tst.exists()
+    for lib in (rel, tst):
+        blob = lib.read_bytes()
+        for name in (b"sw_batch_infix_pileup\0", b"sw_batch_best_hits_pileup\0", b"sw_pileup_export\0"):
+            assert name in blob, (lib.name, name)
+
+
+@pytest.mark.gpu
+def test_the_pileup_passes_on_the_release_library():
+    hooks = ("SEQWIN_AMD_LIB", "SEQWIN_AMD_SCR_TABLE_BITS", "SEQWIN_AMD_HIT_BUFFER_KB", "SEQWIN_AMD_HIT_MAX_BLOCKS", "SEQWIN_AMD_DIST_LDS_CAP",
+             "SEQWIN_AMD_SEQ_MAX_BLOCKS", "SEQWIN_AMD_SCR_MAX_BLOCKS", "SEQWIN_AMD_ALN_SCRATCH_KB")
+    env = {k: v for k, v in os.environ.items() if k not in hooks}
+    env["SEQWIN_AMD_RELEASE_LIB"] = "1"
+    pick = ("test_crafted_pairs or test_shuffled_order or test_one_and_eight_groups or test_a_pair_on_the_bound or test_malformed_calls_raise or "
+            "test_pileup_of_the_winners or test_the_distance_filter or test_markers_best_hits_pileup")
+    r = subprocess.run([sys.executable, "-m", "pytest", str(ROOT / "tests" / "test_gpu_pileup_direct.py"),
+                        str(ROOT / "tests" / "test_gpu_best_hits_pileup.py"), "-x", "-q", "-m", "gpu", "-k", pick, "-p", "no:cacheprovider"],
+                       capture_output=True, text=True, cwd=str(ROOT), env=env, timeout=600)
+    tail = r.stdout[-1500:]
+    assert r.returncode == 0, tail + r.stderr[-1500:]
+    assert " passed" in tail and "failed" not in tail and "skipped" not in tail, tail
+    assert int(tail.split(" passed")[0].split()[-1]) == 10, tail
