@@ -670,6 +670,47 @@ int sw_pileup_depth(const sw_pileup *p, uint32_t *depth);
 int sw_pileup_stats(const sw_pileup *p, uint64_t *counters, double *ms);
 void sw_pileup_free(sw_pileup *p);
 
+/* ---- oligo windows: joint mismatch classes per query window over the canonical alignments, by group (csrc/align.hip, the window walk)
+ * By DESIGN.md section 3.2l (tests/tools/windows_host.py restates it twice).  It is NOT BLAST and no thermodynamic model (no Tm, no
+ * dG), and none of MarkerMetrics is filled.  The table is uint32 W[total query bases][n_lengths][n_groups][8], the queries one behind
+ * the other as in the pileup's table, the row the window's start u in query coordinates; rows with u > m - L stay 0.  The pairs that
+ * count are the pairs the pileup of section 3.2k piles.  Of a piled pair's script (section 3.2f): x[i'] / ins[i'] say that the column
+ * consuming pattern index i' is `X` / `I`, b[i'] (1 <= i' <= m - 1) that a run of `D` lies before i'.  The pattern window [s, s + L)
+ * has e = the sum of x over it and is gapped iff an ins lies in it or a b[i'] with s < i' < s + L; it is the query window at
+ * u = s (strand 0) or m - L - s (strand 1); right_bad / left_bad: an `X` faces one of its last / first three_prime query positions.
+ * The pair adds 1 to exactly one of MM0 0, MM1 1, MM2 2, MM3 3 (ungapped, e = 0..3), MM4P 4 (ungapped, e >= 4), GAPPED 5, and to
+ * FWD_OK 6 (ungapped, e <= max_mismatch, not right_bad) and REV_OK 7 (the same with left_bad) where they hold: classes 0..5 add up to
+ * the pileup's depth at every u <= m - L.  1..8 distinct lengths, each in 8..32, in the order given; max_mismatch in 0..8 and below
+ * the shortest length; three_prime in 0..8; anything else -> SW_ERR_VALUE before a device is touched.  Nothing depends on the order
+ * of the pairs. */
+typedef struct sw_windows sw_windows; /* opaque: the device-resident window table of one call */
+/* sw_batch_infix_pileup -- the same arrays, pileup, checks and errors, counters[8] and ms[3] -- whose walk also classes every window of
+ * the n_lengths lengths (section 3.2l).  One walk fills both tables, so the only thing of the pileup that differs from the call
+ * without windows is a time: sw_pileup_stats' ms[0] (and ms[2] here) is that one walk's, the figure sw_windows_stats gives too. */
+int sw_batch_infix_windows(const sw_batch *b, const uint64_t *offsets, const char *blob, uint64_t n_queries, const sw_infix_pair *pairs, uint64_t n,
+                           const uint8_t *pair_group, uint64_t n_groups, uint64_t max_dist_permille, const uint32_t *lengths, uint64_t n_lengths,
+                           uint64_t max_mismatch, uint64_t three_prime, uint32_t *dist, uint32_t *end, uint32_t *a_start, uint32_t *nident,
+                           uint32_t *mismatch, uint32_t *gaps, sw_pileup **out, sw_windows **windows, uint64_t *counters, double *ms);
+/* sw_batch_best_hits_pileup whose winners' walk also classes every window (section 3.2l).  Everything *out and *pile answer is bit for
+ * bit what the same call without the windows answers, but for the times: the pile walk's is that of the one walk that fills both. */
+int sw_batch_best_hits_windows(const sw_batch *batch, const uint64_t *offsets, const char *blob, uint64_t n_queries, uint64_t k, uint64_t seed_copies,
+                               uint64_t mode, uint64_t min_seeds, const sw_scoring *scoring, const uint8_t *assembly_group, uint64_t n_groups,
+                               uint64_t max_dist_permille, const uint32_t *lengths, uint64_t n_lengths, uint64_t max_mismatch, uint64_t three_prime,
+                               sw_hits **out, sw_pileup **pile, sw_windows **windows);
+/* Section 3.2l: queries, bases of all queries (the table's rows), groups, lengths, max_mismatch, three_prime (any pointer may be NULL). */
+int sw_windows_sizes(const sw_windows *w, uint64_t *n_queries, uint64_t *total_bases, uint64_t *n_groups, uint64_t *n_lengths, uint64_t *max_mismatch,
+                     uint64_t *three_prime);
+/* Section 3.2l: lengths[n_lengths], in the order the call gave them. */
+int sw_windows_lengths(const sw_windows *w, uint32_t *lengths);
+/* Section 3.2l: D2H copy of the rows of queries [q0, q1): out[(bases of those queries) * n_lengths * n_groups * 8].  A range outside
+ * the queries -> SW_ERR_VALUE. */
+int sw_windows_export(const sw_windows *w, uint64_t q0, uint64_t q1, uint32_t *out);
+/* Section 3.2l: counters[3] = { windows visited (of piled pairs, all lengths), adds issued to the table by the walk, table bytes };
+ * ms[2] = { the window walk, the finishing kernel } (HIP events, summed over rounds and chunks).  Either may be NULL. */
+int sw_windows_stats(const sw_windows *w, uint64_t *counters, double *ms);
+/* Section 3.2l. */
+void sw_windows_free(sw_windows *w);
+
 /* ---- oligo search: every place where a primer or probe binds with at most d mismatches, on either strand (csrc/oligo.hip) ----
  * None of this has a counterpart in the reference.  It is NOT BLAST and NOT a thermodynamic model: no Tm, no dG, no e-values; one
  * exactly specified quantity, Hamming distance under IUPAC sets, over EVERY window of the resident batch -- no seed is needed, so no

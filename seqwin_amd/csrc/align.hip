@@ -398,6 +398,217 @@ __global__ __launch_bounds__(SQ_TPB) void k_al_walk_pile(AlArgs a, PileSink s, u
     if (threadIdx.x < PS_N && tally[threadIdx.x]) atomicAdd(s.stat + threadIdx.x, tally[threadIdx.x]);
 }
 
+// The window form of the walk: pile_pair's rules, figures and adds, written out again so that the pile walk
+// keeps its code, plus the class of every window of the sink's lengths.  The walk runs backwards, so three shift registers stand in
+// for the script: after pattern index s = r - 1 is consumed, bit t of X / INS says that the column consuming index s + t is `X` / `I`,
+// and bit t of B that a run of `D` lies before index s + t (a closed run sets bit 0 before the next shift).  With m - s >= L the
+// window [s, s + L) is complete: e = popc(X & maskL); it is gapped iff (INS & maskL) | (B & maskL & ~1) -- a run before index s or
+// s + L lies at the window's edge and does not gap it.  The window's row is u = s on strand 0 and m - L - s on strand 1, where the
+// two tails change ends.  Only an imperfect window adds here (classes 1..5, and 6 / 7 where they hold): k_win_finish fills MM0 from
+// the depth and adds it to FWD_OK and REV_OK.  Every add is an integer atomic whose result nobody reads.
+__device__ void win_pair(const AlArgs &a, const PileSink &s, const WinSink &ws, uint64_t i, unsigned long long *tally, unsigned long long *wtally)
+{
+    const RunTable &t = a.t;
+    const sw_infix_pair p = a.pairs[i];
+    const uint32_t oi = a.out_idx ? a.out_idx[i] : (uint32_t)i;
+    const uint64_t qbase = a.qoff[p.query];
+    const uint32_t m = (uint32_t)(a.qoff[p.query + 1] - qbase), js = a.end[oi] - p.start;
+    const uint32_t strand = p.strand & 1u;
+    const uint32_t *codes = a.codes[strand], *valid = a.valid[strand];
+    const uint64_t tbase = t.rec_base[p.record] + p.start;
+    const uint32_t nb = (m + 63) >> 6;
+    uint32_t d = a.dist[oi];
+    // labels were checked on the host: below n_groups, or PILE_LEAVE_OUT
+    const uint32_t lab = s.group[s.group_mod ? oi % s.group_mod : oi];
+    const bool labelled = lab < s.n_groups, piled = labelled && (uint64_t)d * 1000 <= (uint64_t)s.max_dist_permille * m;
+    const uint64_t stride = (uint64_t)s.n_groups * PILE_CLASSES;
+    uint32_t *const rows = s.table + qbase * stride + (piled ? lab : 0u) * PILE_CLASSES;   // class c of position u: rows[u * stride + c]
+    const uint64_t wstride = (uint64_t)ws.n_lengths * s.n_groups * WIN_CLASSES, lstride = (uint64_t)s.n_groups * WIN_CLASSES;
+    uint32_t *const wrows = ws.table + qbase * wstride + (piled ? lab : 0u) * WIN_CLASSES;   // class c of window u, length l: wrows[u * wstride + l * lstride + c]
+    const uint32_t c3 = ws.three_prime, tail = c3 ? (1u << c3) - 1 : 0u;   // (three_prime <= 8 <= every length)
+    Band band{};
+    if (m && js) band = band_of(m, js, d);
+    const uint64_t base = a.cell_off[i] - a.round_base;
+    RunMemo tm;
+    uint32_t ni = 0, nx = 0, ng = 0, r = m, j = js, run = 0, adds = 0, wadds = 0, seen = 0;
+    uint32_t X = 0, INS = 0, B = 0;
+    uint64_t room = (uint64_t)m + d;   // ops a path of cost dist has at most
+    while (r > 0) {
+        if (room-- == 0) {
+            atomicOr(a.fail, 1u);
+            break;
+        }
+        uint32_t op = 2;   // column 0: D[r][0] = r, only rule 3 is left
+        uint32_t tcls = 4; // the class of text base j - 1 in the query's orientation
+        if (j > 0) {
+            const uint64_t qx = qbase + r - 1;
+            const bool pvalid = (valid[qx >> 5] >> (qx & 31)) & 1u;
+            const uint32_t pc = (uint32_t)load_codes(codes, qx, 1) & 3u;
+            const bool tvalid = valid32(t, p.record, p.start + j - 1, 1, tm) & 1u;
+            const uint32_t tc = (uint32_t)load_codes(t.packed, tbase + j - 1, 1) & 3u;
+            if (tvalid) tcls = strand ? 3u - tc : tc;
+            if (pvalid && tvalid && pc == tc) {
+                op = 0;
+            } else {
+                uint32_t diag;
+                if (r == 1) diag = 0;
+                else if (j == 1) diag = r - 1;
+                else {
+                    const uint32_t Bk = (r - 2) >> 6, bit = (r - 2) & 63u, ob = Bk == nb - 1 ? (m - 1) & 63u : 63u;
+                    const uint64_t slot = band_slot(band, Bk, j - 1);
+                    if (slot == ~0ull) {
+                        atomicOr(a.fail, 1u);
+                        break;
+                    }
+                    const uint64_t at = base + slot;
+                    const uint64_t below = (ob == 63 ? ~0ull : (1ull << (ob + 1)) - 1) & ~((2ull << bit) - 1);   // rows bit + 1 .. ob
+                    diag = a.sc[at] - (uint32_t)__popcll(a.pv[at] & below) + (uint32_t)__popcll(a.mv[at] & below);
+                }
+                if (diag + 1 == d) op = 1;
+                else {
+                    const uint64_t slot = band_slot(band, (r - 1) >> 6, j);
+                    if (slot == ~0ull) {
+                        atomicOr(a.fail, 1u);
+                        break;
+                    }
+                    const uint64_t at = base + slot;
+                    op = ((a.pv[at] >> ((r - 1) & 63u)) & 1ull) ? 2 : 3;
+                }
+            }
+        }
+        if (piled) {
+            if (op == 3) ++run;
+            else {
+                if (run) {
+                    // the run lies before pattern index r, which is neither 0 (the walk would have stopped) nor m (j* is the smallest
+                    // column of the minimum): its slot lies inside the query's rows
+                    if (r >= m) {
+                        atomicOr(a.fail, 1u);
+                        break;
+                    }
+                    uint32_t *const slot = rows + (uint64_t)(strand ? m - r : r) * stride;
+                    atomicAdd(slot + 6, 1u);
+                    atomicAdd(slot + 7, run);
+                    adds += 2;
+                    run = 0;
+                    B |= 1u;   // bit 0 is still index r, the last one consumed
+                }
+                atomicAdd(rows + (uint64_t)(strand ? m - r : r - 1) * stride + (op == 2 ? 5u : tcls), 1u);
+                ++adds;
+                // index r - 1 is consumed: it becomes bit 0
+                X = (X << 1) | (op == 1 ? 1u : 0u);
+                INS = (INS << 1) | (op == 2 ? 1u : 0u);
+                B <<= 1;
+                const uint32_t ws0 = r - 1, left = m - ws0;   // the pattern indices from ws0 on
+                for (uint32_t l = 0; l < ws.n_lengths; ++l) {
+                    const uint32_t L = ws.len[l];
+                    if (left < L) continue;
+                    ++seen;
+                    const uint32_t mask = L >= 32 ? ~0u : (1u << L) - 1;
+                    const uint32_t xm = X & mask;
+                    // (B was shifted just above, so its bit 0 is 0 here and `& ~1u` removes nothing: it stands as section 3.2l words the test)
+                    const bool gapped = ((INS & mask) | (B & mask & ~1u)) != 0;
+                    if (!gapped && !xm) continue;   // a perfect window: the finishing pass counts it
+                    const uint32_t u = strand ? left - L : ws0;   // u + L <= m by left >= L
+                    if ((uint64_t)u + L > m) {
+                        atomicOr(a.fail, 1u);
+                        continue;
+                    }
+                    uint32_t *const slot = wrows + (uint64_t)u * wstride + (uint64_t)l * lstride;
+                    if (gapped) {
+                        atomicAdd(slot + 5, 1u);
+                        ++wadds;
+                        continue;
+                    }
+                    const uint32_t e = (uint32_t)__popc(xm);
+                    atomicAdd(slot + (e < 4 ? e : 4u), 1u);
+                    ++wadds;
+                    if (e <= ws.max_mismatch) {
+                        // pattern indices rise with the query's positions on strand 0 and fall with them on strand 1
+                        const bool low_bad = (xm & tail) != 0, high_bad = c3 && ((xm >> (L - c3)) & tail) != 0;
+                        const bool right_bad = strand ? low_bad : high_bad, left_bad = strand ? high_bad : low_bad;
+                        if (!right_bad) {
+                            atomicAdd(slot + 6, 1u);
+                            ++wadds;
+                        }
+                        if (!left_bad) {
+                            atomicAdd(slot + 7, 1u);
+                            ++wadds;
+                        }
+                    }
+                }
+            }
+        }
+        if (op == 0) ++ni;
+        else if (op == 1) ++nx;
+        else ++ng;
+        if (op != 0) --d;
+        if (op != 3) --r;
+        if (op != 2) --j;
+    }
+    if (run) atomicOr(a.fail, 1u);   // (a script does not begin with D)
+    a.a_start[oi] = p.start + j;
+    a.nident[oi] = ni;
+    a.mismatch[oi] = nx;
+    a.gaps[oi] = ng;
+    if (piled) {
+        atomicAdd(s.depth + (uint64_t)p.query * s.n_groups + lab, 1u);
+        atomicAdd(tally + PS_ADDS, (unsigned long long)adds);
+        atomicAdd(wtally + WS_WINDOWS, (unsigned long long)seen);
+        atomicAdd(wtally + WS_ADDS, (unsigned long long)wadds);
+    }
+    atomicAdd(tally + (piled ? PS_PILED : labelled ? PS_FILTERED : PS_LEFT_OUT), 1ull);
+}
+
+// pairs [p0, p1) of the list, one lane each; the workgroup's counters go to the sinks' in one add each
+__global__ __launch_bounds__(SQ_TPB) void k_al_walk_win(AlArgs a, PileSink s, WinSink ws, uint64_t p0, uint64_t p1)
+{
+    __shared__ unsigned long long tally[PS_N], wtally[WS_N];
+    if (threadIdx.x < PS_N) tally[threadIdx.x] = 0;
+    if (threadIdx.x < WS_N) wtally[threadIdx.x] = 0;
+    __syncthreads();
+    const uint64_t i = p0 + (uint64_t)blockIdx.x * SQ_TPB + threadIdx.x;
+    if (i < p1) win_pair(a, s, ws, i, tally, wtally);
+    __syncthreads();
+    if (threadIdx.x < PS_N && tally[threadIdx.x]) atomicAdd(s.stat + threadIdx.x, tally[threadIdx.x]);
+    if (threadIdx.x < WS_N && wtally[threadIdx.x]) atomicAdd(ws.stat + threadIdx.x, wtally[threadIdx.x]);
+}
+
+// One thread per (row, length, group) of the window table, after the last walk: MM0 = depth - (MM1 + .. + GAPPED) at every window
+// start u <= m - L, and MM0 more to FWD_OK and REV_OK (a perfect window is both).  Rows behind m - L stay 0.
+__global__ __launch_bounds__(SQ_TPB) void k_win_finish(uint32_t *__restrict__ table, const uint32_t *__restrict__ depth, const uint64_t *__restrict__ qoff, uint64_t nq,
+                                                       uint32_t n_groups, WinSink ws, uint64_t x0, uint64_t x1, uint32_t *__restrict__ fail)
+{
+    const uint64_t x = x0 + (uint64_t)blockIdx.x * SQ_TPB + threadIdx.x;
+    if (x >= x1) return;
+    const uint64_t per_row = (uint64_t)ws.n_lengths * n_groups, row = x / per_row;
+    const uint32_t l = (uint32_t)((x % per_row) / n_groups), g = (uint32_t)(x % n_groups);
+    // the query of the row: the last q with qoff[q] <= row (empty queries share an offset with the next one)
+    uint64_t lo = 0, hi = nq;
+    while (hi - lo > 1) {
+        const uint64_t mid = (lo + hi) >> 1;
+        if (qoff[mid] <= row) lo = mid;
+        else hi = mid;
+    }
+    const uint64_t m = qoff[lo + 1] - qoff[lo], u = row - qoff[lo];
+    if (row < qoff[lo] || u >= m) {
+        atomicOr(fail, 1u);
+        return;
+    }
+    const uint32_t L = ws.len[l];
+    if (m < L || u > m - L) return;
+    uint32_t *const c = table + x * WIN_CLASSES;
+    const uint32_t other = c[1] + c[2] + c[3] + c[4] + c[5], dep = depth[lo * n_groups + g];
+    if (other > dep) {
+        atomicOr(fail, 1u);
+        return;
+    }
+    const uint32_t mm0 = dep - other;
+    c[0] = mm0;
+    c[6] += mm0;
+    c[7] += mm0;
+}
+
 // script of pair x: ops [off[x], off[x + 1]) of the output, the last bytes of its padded slot
 __global__ __launch_bounds__(SQ_TPB) void k_al_compact(uint64_t b0, uint64_t total, const uint64_t *__restrict__ off, uint32_t n, const uint64_t *__restrict__ pad_end,
                                                        const uint8_t *__restrict__ padded, uint8_t *__restrict__ out)
@@ -415,9 +626,11 @@ __global__ __launch_bounds__(SQ_TPB) void k_al_compact(uint64_t b0, uint64_t tot
 }  // namespace
 
 void align_device(const Runs &runs, const QueryPack &P, const sw_infix_pair *d_pairs, const uint32_t *d_out_idx, uint64_t n, const uint32_t *d_dist,
-                  const uint32_t *d_end, uint32_t *const out[4], uint8_t *d_ops, const uint64_t *d_ops_end, AlignStats &st, const PileSink *pile)
+                  const uint32_t *d_end, uint32_t *const out[4], uint8_t *d_ops, const uint64_t *d_ops_end, AlignStats &st, const PileSink *pile,
+                  const WinSink *win)
 {
     if (!n) return;
+    if (win && !pile) raise(SW_ERR_RUNTIME, "internal error: the window walk needs the pileup's sink");
     if (n > SQ_MAX_LIST) raise(SW_ERR_VALUE, "infix alignments: %llu pairs exceed one launch of the list kernels (%llu)", (unsigned long long)n, (unsigned long long)SQ_MAX_LIST);
     const hipStream_t stream = HIT_STREAM;
     const uint32_t cap = ed_cap_blocks();
@@ -541,7 +754,8 @@ void align_device(const Runs &runs, const QueryPack &P, const sw_infix_pair *d_p
         SW_HIP(hipEventRecord(e1, stream));
         for (uint64_t x0 = p0; x0 < p1; x0 += max_threads) {
             const uint64_t x1 = std::min<uint64_t>(p1, x0 + max_threads);
-            if (pile) hipLaunchKernelGGL(k_al_walk_pile, dim3(sq_blocks(x1 - x0)), dim3(SQ_TPB), 0, stream, a, *pile, x0, x1);
+            if (win) hipLaunchKernelGGL(k_al_walk_win, dim3(sq_blocks(x1 - x0)), dim3(SQ_TPB), 0, stream, a, *pile, *win, x0, x1);
+            else if (pile) hipLaunchKernelGGL(k_al_walk_pile, dim3(sq_blocks(x1 - x0)), dim3(SQ_TPB), 0, stream, a, *pile, x0, x1);
             else hipLaunchKernelGGL(k_al_walk, dim3(sq_blocks(x1 - x0)), dim3(SQ_TPB), 0, stream, a, x0, x1);
             SW_HIP(hipGetLastError());
         }
@@ -616,6 +830,87 @@ void pile_finish(sw_pileup &p, double walk_ms)
     p.labels.release();
     p.stat.release();
     p.sink = PileSink{};
+}
+
+// ---- the oligo windows' table -----------------------------------------------------------------------------
+void check_win_args(const char *what, const uint32_t *lengths, uint64_t n_lengths, uint64_t max_mismatch, uint64_t three_prime)
+{
+    if (n_lengths < 1 || n_lengths > WIN_MAX_LENGTHS)
+        raise(SW_ERR_VALUE, "%s: the windows take 1..%u lengths (got %llu)", what, WIN_MAX_LENGTHS, (unsigned long long)n_lengths);
+    if (!lengths) raise(SW_ERR_VALUE, "%s: a NULL handle or array", what);
+    uint32_t shortest = 32;
+    for (uint64_t i = 0; i < n_lengths; ++i) {
+        if (lengths[i] < 8 || lengths[i] > 32) raise(SW_ERR_VALUE, "%s: window length %u lies outside 8..32", what, lengths[i]);
+        for (uint64_t j = 0; j < i; ++j)
+            if (lengths[j] == lengths[i]) raise(SW_ERR_VALUE, "%s: window length %u is given twice", what, lengths[i]);
+        shortest = std::min(shortest, lengths[i]);
+    }
+    if (max_mismatch > 8 || max_mismatch >= shortest)
+        raise(SW_ERR_VALUE, "%s: max_mismatch must lie in 0..8 and below the shortest window length %u (got %llu)", what, shortest,
+              (unsigned long long)max_mismatch);
+    if (three_prime > 8) raise(SW_ERR_VALUE, "%s: three_prime must lie in 0..8 (got %llu)", what, (unsigned long long)three_prime);
+}
+
+void win_begin(sw_windows &w, int device, const uint64_t *offsets, uint64_t nq, uint64_t n_groups, const uint32_t *lengths, uint64_t n_lengths,
+               uint64_t max_mismatch, uint64_t three_prime)
+{
+    const hipStream_t stream = HIT_STREAM;
+    w.device = device;
+    w.nq = nq;
+    w.n_groups = n_groups;
+    w.n_lengths = n_lengths;
+    w.max_mismatch = max_mismatch;
+    w.three_prime = three_prime;
+    w.off.assign(offsets, offsets + nq + 1);
+    const uint64_t cells = w.off[nq] * n_lengths * n_groups * WIN_CLASSES;   // (below 2^32 rows * 8 * 8 * 8: no overflow in 64 bits)
+    w.table.alloc(cells);
+    w.d_off.alloc(nq + 1);
+    w.stat.alloc(WS_N);
+    if (cells) SW_HIP(hipMemsetAsync(w.table.p, 0, cells * 4, stream));
+    SW_HIP(hipMemcpyAsync(w.d_off.p, w.off.data(), (nq + 1) * 8, hipMemcpyHostToDevice, stream));
+    SW_HIP(hipMemsetAsync(w.stat.p, 0, WS_N * sizeof(unsigned long long), stream));
+    SW_HIP(hipStreamSynchronize(stream));
+    w.sink = WinSink{};
+    w.sink.table = w.table.p;
+    for (uint64_t i = 0; i < n_lengths; ++i) w.sink.len[i] = w.lengths[i] = lengths[i];
+    w.sink.n_lengths = (uint32_t)n_lengths;
+    w.sink.max_mismatch = (uint32_t)max_mismatch;
+    w.sink.three_prime = (uint32_t)three_prime;
+    w.sink.stat = w.stat.p;
+    w.counters[2] = cells * 4;
+}
+
+void win_finish(sw_windows &w, const sw_pileup &p, double walk_ms)
+{
+    const hipStream_t stream = HIT_STREAM;
+    const uint64_t items = w.off[w.nq] * w.n_lengths * w.n_groups;
+    DevArray<uint32_t> d_fail(1);
+    SW_HIP(hipMemsetAsync(d_fail.p, 0, 4, stream));
+    Event e0, e1;
+    SW_HIP(hipEventRecord(e0, stream));
+    const uint64_t max_threads = (uint64_t)launch_blocks(SQ_BLOCKS_ENV) * SQ_TPB;
+    for (uint64_t x0 = 0; x0 < items; x0 += max_threads) {
+        const uint64_t x1 = std::min<uint64_t>(items, x0 + max_threads);
+        hipLaunchKernelGGL(k_win_finish, dim3(sq_blocks(x1 - x0)), dim3(SQ_TPB), 0, stream, w.table.p, (const uint32_t *)p.depth.p, (const uint64_t *)w.d_off.p, w.nq,
+                           (uint32_t)w.n_groups, w.sink, x0, x1, d_fail.p);
+        SW_HIP(hipGetLastError());
+    }
+    SW_HIP(hipEventRecord(e1, stream));
+    unsigned long long st[WS_N] = {};
+    uint32_t failed = 0;
+    SW_HIP(hipMemcpyAsync(st, w.stat.p, sizeof st, hipMemcpyDeviceToHost, stream));
+    SW_HIP(hipMemcpyAsync(&failed, d_fail.p, 4, hipMemcpyDeviceToHost, stream));
+    SW_HIP(hipStreamSynchronize(stream));
+    if (failed) raise(SW_ERR_RUNTIME, "internal error: a window's classes exceed the depth of its query");
+    float ms = 0;
+    SW_HIP(hipEventElapsedTime(&ms, e0, e1));
+    w.counters[WS_WINDOWS] = st[WS_WINDOWS];
+    w.counters[WS_ADDS] = st[WS_ADDS];
+    w.ms[0] = walk_ms;
+    w.ms[1] = ms;
+    w.d_off.release();
+    w.stat.release();
+    w.sink = WinSink{};
 }
 
 }  // namespace sw
@@ -726,15 +1021,22 @@ void sw_ops_free(sw_ops *o)
     delete o;
 }
 
-int sw_batch_infix_pileup(const sw_batch *b, const uint64_t *offsets, const char *blob, uint64_t n_queries, const sw_infix_pair *pairs, uint64_t n,
-                          const uint8_t *pair_group, uint64_t n_groups, uint64_t max_dist_permille, uint32_t *dist, uint32_t *end, uint32_t *a_start,
-                          uint32_t *nident, uint32_t *mismatch, uint32_t *gaps, sw_pileup **out, uint64_t *counters, double *ms)
+// the window arguments of a call; without them the call is the pileup's
+struct WinSpec {
+    const uint32_t *lengths;
+    uint64_t n_lengths, max_mismatch, three_prime;
+    sw_windows **out;
+};
+
+static int infix_pileup_entry(const char *what, const sw_batch *b, const uint64_t *offsets, const char *blob, uint64_t n_queries, const sw_infix_pair *pairs, uint64_t n,
+                              const uint8_t *pair_group, uint64_t n_groups, uint64_t max_dist_permille, uint32_t *dist, uint32_t *end, uint32_t *a_start,
+                              uint32_t *nident, uint32_t *mismatch, uint32_t *gaps, sw_pileup **out, uint64_t *counters, double *ms, const WinSpec *win)
 {
     return guarded([&] {
-        const char *what = "infix pileup";
         check_queries(what, offsets, blob, n_queries);
         check_pile_args(what, n_groups, max_dist_permille, pair_group, n, n, offsets, n_queries);
-        if (!out) raise(SW_ERR_VALUE, "%s: a NULL handle or array", what);
+        if (win) check_win_args(what, win->lengths, win->n_lengths, win->max_mismatch, win->three_prime);
+        if (!out || (win && !win->out)) raise(SW_ERR_VALUE, "%s: a NULL handle or array", what);
         check_infix_pairs(what, b, offsets, blob, n_queries, pairs, n, dist && end && a_start && nident && mismatch && gaps);
         StreamScope scope(HIT_STREAM);
         DevRuns runs(*b);
@@ -752,9 +1054,12 @@ int sw_batch_infix_pileup(const sw_batch *b, const uint64_t *offsets, const char
         const uint64_t no_query[1] = {0};
         std::unique_ptr<sw_pileup> p(new sw_pileup);
         pile_begin(*p, b->device, n_queries ? offsets : no_query, n_queries, n_groups, max_dist_permille, pair_group, n, 0);
+        std::unique_ptr<sw_windows> w(win ? new sw_windows : nullptr);
+        if (win) win_begin(*w, b->device, n_queries ? offsets : no_query, n_queries, n_groups, win->lengths, win->n_lengths, win->max_mismatch, win->three_prime);
         AlignStats st;
         uint32_t *const dev[4] = {d_out[0].p, d_out[1].p, d_out[2].p, d_out[3].p};
-        align_device(runs_of(runs.t), P, d_pairs.p, nullptr, n, d_dist.p, d_end.p, dev, nullptr, nullptr, st, &p->sink);
+        align_device(runs_of(runs.t), P, d_pairs.p, nullptr, n, d_dist.p, d_end.p, dev, nullptr, nullptr, st, &p->sink, win ? &w->sink : nullptr);
+        if (win) win_finish(*w, *p, st.ms[1]);
         pile_finish(*p, st.ms[1]);
         uint32_t *const host[6] = {dist, end, a_start, nident, mismatch, gaps};
         const uint32_t *const from[6] = {d_dist.p, d_end.p, d_out[0].p, d_out[1].p, d_out[2].p, d_out[3].p};
@@ -767,7 +1072,83 @@ int sw_batch_infix_pileup(const sw_batch *b, const uint64_t *offsets, const char
             ms[2] = st.ms[1];
         }
         *out = p.release();
+        if (win) *win->out = w.release();
     });
+}
+
+int sw_batch_infix_pileup(const sw_batch *b, const uint64_t *offsets, const char *blob, uint64_t n_queries, const sw_infix_pair *pairs, uint64_t n,
+                          const uint8_t *pair_group, uint64_t n_groups, uint64_t max_dist_permille, uint32_t *dist, uint32_t *end, uint32_t *a_start,
+                          uint32_t *nident, uint32_t *mismatch, uint32_t *gaps, sw_pileup **out, uint64_t *counters, double *ms)
+{
+    return infix_pileup_entry("infix pileup", b, offsets, blob, n_queries, pairs, n, pair_group, n_groups, max_dist_permille, dist, end, a_start, nident, mismatch,
+                              gaps, out, counters, ms, nullptr);
+}
+
+int sw_batch_infix_windows(const sw_batch *b, const uint64_t *offsets, const char *blob, uint64_t n_queries, const sw_infix_pair *pairs, uint64_t n,
+                           const uint8_t *pair_group, uint64_t n_groups, uint64_t max_dist_permille, const uint32_t *lengths, uint64_t n_lengths,
+                           uint64_t max_mismatch, uint64_t three_prime, uint32_t *dist, uint32_t *end, uint32_t *a_start, uint32_t *nident,
+                           uint32_t *mismatch, uint32_t *gaps, sw_pileup **out, sw_windows **windows, uint64_t *counters, double *ms)
+{
+    const WinSpec win{lengths, n_lengths, max_mismatch, three_prime, windows};
+    return infix_pileup_entry("infix windows", b, offsets, blob, n_queries, pairs, n, pair_group, n_groups, max_dist_permille, dist, end, a_start, nident, mismatch,
+                              gaps, out, counters, ms, &win);
+}
+
+static const sw_windows &windows_of(const sw_windows *w)
+{
+    if (!w) raise(SW_ERR_VALUE, "windows: a NULL handle");
+    return *w;
+}
+
+int sw_windows_sizes(const sw_windows *w, uint64_t *n_queries, uint64_t *total_bases, uint64_t *n_groups, uint64_t *n_lengths, uint64_t *max_mismatch,
+                     uint64_t *three_prime)
+{
+    return guarded([&] {
+        const sw_windows &x = windows_of(w);
+        if (n_queries) *n_queries = x.nq;
+        if (total_bases) *total_bases = x.off[x.nq];
+        if (n_groups) *n_groups = x.n_groups;
+        if (n_lengths) *n_lengths = x.n_lengths;
+        if (max_mismatch) *max_mismatch = x.max_mismatch;
+        if (three_prime) *three_prime = x.three_prime;
+    });
+}
+
+int sw_windows_lengths(const sw_windows *w, uint32_t *lengths)
+{
+    return guarded([&] {
+        const sw_windows &x = windows_of(w);
+        if (!lengths) raise(SW_ERR_VALUE, "windows: a NULL handle or array");
+        for (uint64_t i = 0; i < x.n_lengths; ++i) lengths[i] = x.lengths[i];
+    });
+}
+
+int sw_windows_export(const sw_windows *w, uint64_t q0, uint64_t q1, uint32_t *out)
+{
+    return guarded([&] {
+        const sw_windows &x = windows_of(w);
+        if (q0 > q1 || q1 > x.nq)
+            raise(SW_ERR_VALUE, "windows: queries [%llu, %llu) lie outside the %llu queries", (unsigned long long)q0, (unsigned long long)q1, (unsigned long long)x.nq);
+        const uint64_t per = x.n_lengths * x.n_groups * WIN_CLASSES, cells = (x.off[q1] - x.off[q0]) * per;
+        if (!cells) return;
+        if (!out) raise(SW_ERR_VALUE, "windows: a NULL handle or array");
+        require_device(x.device, "the windows");
+        SW_HIP(hipMemcpy(out, x.table.p + x.off[q0] * per, cells * 4, hipMemcpyDeviceToHost));
+    });
+}
+
+int sw_windows_stats(const sw_windows *w, uint64_t *counters, double *ms)
+{
+    return guarded([&] {
+        const sw_windows &x = windows_of(w);
+        if (counters) memcpy(counters, x.counters, sizeof x.counters);
+        if (ms) memcpy(ms, x.ms, sizeof x.ms);
+    });
+}
+
+void sw_windows_free(sw_windows *w)
+{
+    delete w;
 }
 
 static const sw_pileup &pile_of(const sw_pileup *p)

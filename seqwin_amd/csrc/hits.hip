@@ -872,10 +872,15 @@ namespace {
 // right behind their distances; nullptr: not one pass more than before
 // pile != nullptr (it needs align): the winners' traceback also adds every piled winner to the pileup's tables (align.hip, DESIGN.md
 // section 3.2k), labelled by its assembly; the loci's traceback stays the plain one
+// pile->lengths != nullptr: the winners' traceback is the window walk, which also classes every window of those lengths (DESIGN.md
+// section 3.2l)
 struct PileCall {
     sw_pileup *p;
     const uint8_t *assembly_group;
     uint64_t n_groups, max_dist_permille;
+    sw_windows *w = nullptr;
+    const uint32_t *lengths = nullptr;
+    uint64_t n_lengths = 0, max_mismatch = 0, three_prime = 0;
 };
 
 void batch_best_hits(const sw_batch &b, const uint64_t *offsets, const char *blob, uint64_t nq, uint32_t k, bool align, uint64_t min_seeds, uint32_t seed_copies,
@@ -906,6 +911,8 @@ void batch_best_hits(const sw_batch &b, const uint64_t *offsets, const char *blo
     if (pile) {
         const uint64_t no_query[1] = {0};
         pile_begin(*pile->p, b.device, nq ? offsets : no_query, nq, pile->n_groups, pile->max_dist_permille, pile->assembly_group, n_asm, n_asm);
+        if (pile->w)
+            win_begin(*pile->w, b.device, nq ? offsets : no_query, nq, pile->n_groups, pile->lengths, pile->n_lengths, pile->max_mismatch, pile->three_prime);
     }
     o.has_local = local != nullptr;
     if (local)
@@ -1119,7 +1126,7 @@ void batch_best_hits(const sw_batch &b, const uint64_t *offsets, const char *blo
                 if (align) {
                     uint32_t *const out[4] = {o.afield[0].p, o.afield[1].p, o.afield[2].p, o.afield[3].p};
                     align_device(runs_of(runs.t), P, pairs.p, out_idx.p, n_pairs, o.field[4].p, o.field[3].p, out, nullptr, nullptr, o.align,
-                                 pile ? &pile->p->sink : nullptr);
+                                 pile ? &pile->p->sink : nullptr, pile && pile->w ? &pile->w->sink : nullptr);
                 }
                 if (local) {
                     uint32_t *lout[LOCAL_FIELDS];
@@ -1166,6 +1173,7 @@ void batch_best_hits(const sw_batch &b, const uint64_t *offsets, const char *blo
         }
     }
     SW_HIP(hipStreamSynchronize(stream));
+    if (pile && pile->w) win_finish(*pile->w, *pile->p, o.align.ms[1]);
     if (pile) pile_finish(*pile->p, o.align.ms[1]);
     if (loci) {
         Event f0, f1;
@@ -1210,7 +1218,8 @@ namespace {
 
 // min_seeds: nullptr without the loci mode; seed_copies: nullptr for the unique-seed route
 void best_hits_entry(const sw_batch *batch, const uint64_t *offsets, const char *blob, uint64_t n_queries, uint64_t k, bool align, const uint64_t *min_seeds,
-                     sw_hits **out, const uint64_t *seed_copies = nullptr, const sw_scoring *local = nullptr, PileCall *pile = nullptr, sw_pileup **pile_out = nullptr)
+                     sw_hits **out, const uint64_t *seed_copies = nullptr, const sw_scoring *local = nullptr, PileCall *pile = nullptr, sw_pileup **pile_out = nullptr,
+                     sw_windows **win_out = nullptr)
 {
     if (k < 1 || k > 32) raise(SW_ERR_VALUE, "best hits: k-mer length must lie in 1..32 (got %llu)", (unsigned long long)k);
     if (seed_copies && (*seed_copies < 1 || *seed_copies > 256))
@@ -1224,7 +1233,7 @@ void best_hits_entry(const sw_batch *batch, const uint64_t *offsets, const char 
                 raise(SW_ERR_VALUE, "best hits: query %llu has %llu bases, above the 65279 the local alignment takes", (unsigned long long)q,
                       (unsigned long long)(offsets[q + 1] - offsets[q]));
     if (pile) {
-        if (!pile_out) raise(SW_ERR_VALUE, "best hits: a NULL handle or array");
+        if (!pile_out || (pile->lengths && !win_out)) raise(SW_ERR_VALUE, "best hits: a NULL handle or array");
         check_pile_args("best hits", pile->n_groups, pile->max_dist_permille, pile->assembly_group, batch->host.n_assemblies, batch->host.n_assemblies, offsets,
                         n_queries);
     }
@@ -1233,11 +1242,14 @@ void best_hits_entry(const sw_batch *batch, const uint64_t *offsets, const char 
     StreamScope scope(HIT_STREAM);
     std::unique_ptr<sw_hits> o(new sw_hits);
     std::unique_ptr<sw_pileup> po(pile ? new sw_pileup : nullptr);
+    std::unique_ptr<sw_windows> wo(pile && pile->lengths ? new sw_windows : nullptr);
     if (pile) pile->p = po.get();
+    if (pile) pile->w = wo.get();
     o->device = batch->device;
     batch_best_hits(*batch, offsets, blob, n_queries, (uint32_t)k, align, min_seeds ? *min_seeds : 0, seed_copies ? (uint32_t)*seed_copies : 0u, local, *o, pile);
     *out = o.release();
     if (pile) *pile_out = po.release();
+    if (wo) *win_out = wo.release();
 }
 
 }  // namespace
@@ -1315,6 +1327,22 @@ int sw_batch_best_hits_pileup(const sw_batch *batch, const uint64_t *offsets, co
         check_pile_args("best hits", n_groups, max_dist_permille, nullptr, 0, 0, nullptr, 0);
         PileCall pc{nullptr, assembly_group, n_groups, max_dist_permille};
         best_hits_entry(batch, offsets, blob, n_queries, k, true, mode == 2 ? &min_seeds : nullptr, out, seed_copies ? &seed_copies : nullptr, scoring, &pc, pile);
+    });
+}
+
+int sw_batch_best_hits_windows(const sw_batch *batch, const uint64_t *offsets, const char *blob, uint64_t n_queries, uint64_t k, uint64_t seed_copies,
+                               uint64_t mode, uint64_t min_seeds, const sw_scoring *scoring, const uint8_t *assembly_group, uint64_t n_groups,
+                               uint64_t max_dist_permille, const uint32_t *lengths, uint64_t n_lengths, uint64_t max_mismatch, uint64_t three_prime,
+                               sw_hits **out, sw_pileup **pile, sw_windows **windows)
+{
+    return guarded([&] {
+        if (mode > 2) raise(SW_ERR_VALUE, "best hits: mode %llu is none of plain, aligned, loci (0..2)", (unsigned long long)mode);
+        if (scoring) check_scoring("best hits", scoring);
+        check_pile_args("best hits", n_groups, max_dist_permille, nullptr, 0, 0, nullptr, 0);
+        check_win_args("best hits", lengths, n_lengths, max_mismatch, three_prime);
+        PileCall pc{nullptr, assembly_group, n_groups, max_dist_permille, nullptr, lengths, n_lengths, max_mismatch, three_prime};
+        best_hits_entry(batch, offsets, blob, n_queries, k, true, mode == 2 ? &min_seeds : nullptr, out, seed_copies ? &seed_copies : nullptr, scoring, &pc, pile,
+                        windows);
     });
 }
 

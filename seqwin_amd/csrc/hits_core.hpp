@@ -59,6 +59,18 @@ struct PileSink {
     unsigned long long *stat;    // [PS_N]
 };
 
+// The oligo windows' sink of a traceback (align.hip): where the window walk adds the class of every imperfect
+// window of a piled pair.  It always travels with a PileSink, whose labels, groups and bound decide which pairs count.
+constexpr uint32_t WIN_CLASSES = 8;       // MM0, MM1, MM2, MM3, MM4P, GAPPED, FWD_OK, REV_OK
+constexpr uint32_t WIN_MAX_LENGTHS = 8;
+enum { WS_WINDOWS, WS_ADDS, WS_N };
+struct WinSink {
+    uint32_t *table;             // [total query bases][n_lengths][n_groups][WIN_CLASSES]
+    uint32_t len[WIN_MAX_LENGTHS];
+    uint32_t n_lengths, max_mismatch, three_prime;
+    unsigned long long *stat;    // [WS_N]
+};
+
 // RunTable (seqs_core.hpp) has internal linkage like every type of that header; this is the same table as the two files hand it to
 // each other (runs_of / table_of below)
 struct Runs {
@@ -80,15 +92,23 @@ void check_infix_pairs(const char *what, const sw_batch *b, const uint64_t *offs
 // at d_ops[d_ops_end[i]] (exclusive), the slot in front of it holding |query| + dist bytes.  st is added to.
 // pile != nullptr: the pile walk stands in for the plain walk -- the same four figures, and every piled pair's columns added to the
 // sink; nullptr: not one kernel or argument differs from a call made before the pileup existed.
+// win != nullptr (it needs pile): the window walk stands in for the pile walk -- the same figures and the same adds to pile, and every
+// imperfect window of a piled pair added to win; nullptr: not one kernel or argument differs from a call made before the windows existed.
 void align_device(const Runs &t, const QueryPack &P, const sw_infix_pair *d_pairs, const uint32_t *d_out_idx, uint64_t n, const uint32_t *d_dist,
                   const uint32_t *d_end, uint32_t *const out[4], uint8_t *d_ops, const uint64_t *d_ops_end, AlignStats &st,
-                  const PileSink *pile = nullptr);
+                  const PileSink *pile = nullptr, const WinSink *win = nullptr);
 // align.hip: the pileup's argument checks (before a device is touched), its zeroed tables, the sink that adds to them, its counters
 void check_pile_args(const char *what, uint64_t n_groups, uint64_t max_dist_permille, const uint8_t *labels, uint64_t n_labels, uint64_t n_piles,
                      const uint64_t *offsets, uint64_t nq);
 void pile_begin(sw_pileup &p, int device, const uint64_t *offsets, uint64_t nq, uint64_t n_groups, uint64_t max_dist_permille, const uint8_t *labels,
                 uint64_t n_labels, uint64_t group_mod);
 void pile_finish(sw_pileup &p, double walk_ms);
+// align.hip: the oligo windows' argument checks (before a device is touched), their zeroed table and sink, and the finishing pass
+// that fills MM0 from the pileup's depths (after the last walk, before pile_finish)
+void check_win_args(const char *what, const uint32_t *lengths, uint64_t n_lengths, uint64_t max_mismatch, uint64_t three_prime);
+void win_begin(sw_windows &w, int device, const uint64_t *offsets, uint64_t nq, uint64_t n_groups, const uint32_t *lengths, uint64_t n_lengths,
+               uint64_t max_mismatch, uint64_t three_prime);
+void win_finish(sw_windows &w, const sw_pileup &p, double walk_ms);
 
 // local.hip: the nine figures of n valid pairs (device list) under scoring system sc, written at the pair's out index; every side
 // of a pair is below 2^16 (the callers check it on the host).  st is added to.
@@ -127,6 +147,19 @@ struct sw_pileup {
     sw::PileSink sink{};
     uint64_t counters[5] = {};                     // pairs piled, filtered by distance, left out by label, adds issued, table bytes
     double ms = 0;                                 // the pile walk
+};
+
+struct sw_windows {
+    int device = 0;
+    uint64_t nq = 0, n_groups = 0, n_lengths = 0, max_mismatch = 0, three_prime = 0;
+    uint32_t lengths[sw::WIN_MAX_LENGTHS] = {};
+    std::vector<uint64_t> off;                     // [nq + 1]: the rows of query q are [off[q], off[q + 1])
+    sw::DevArray<uint32_t> table;
+    sw::DevArray<uint64_t> d_off;                  // off on the device, for the finishing pass
+    sw::DevArray<unsigned long long> stat;
+    sw::WinSink sink{};
+    uint64_t counters[3] = {};                     // windows visited, adds issued, table bytes
+    double ms[2] = {};                             // the window walk, the finishing kernel
 };
 
 struct sw_hits {

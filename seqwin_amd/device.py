@@ -200,6 +200,32 @@ class Batch:
                                         *[_ptr(a) for a in out], ctypes.byref(h), None, None))
         return Pileup(h, offs), tuple(out)
 
+    def infix_windows(self, queries, pairs, groups, lengths, n_groups=None, max_dist_permille: int = 1000, max_mismatch: int = 2, three_prime: int = 3,
+                      stats: bool = False):
+        """``(Windows, Pileup, (dist, end, start, nident, mismatch, gaps))``: :meth:`infix_pileup` -- the same pileup and arrays, bit
+        for bit -- whose walk also classes, per window start of every query, window length and group, how the piled pairs' copies
+        match the window JOINTLY (csrc/align.hip, DESIGN.md section 3.2l).  ``lengths``: 1..8 distinct window lengths, each in 8..32;
+        ``max_mismatch`` in 0..8 and below the shortest length; ``three_prime`` in 0..8: the bases at an oligo's 3' end that must not
+        face a mismatch.  Anything else is a ValueError before a device is touched.  Exact counts that do not depend on the order
+        of the pairs.  Not BLAST and no thermodynamic model: no Tm, no dG.  ``stats=True`` adds the counters and times of the
+        alignment behind the tables last, as :meth:`infix_alignments` names them; ``walk_ms`` is the one walk that fills both tables."""
+        offs, blob, nq = _query_csr(queries)
+        pr = _infix_pairs(pairs)
+        lab, ng = _pile_groups(groups, len(pr), n_groups, "pair")
+        lens, mm, c3 = _window_args(lengths, max_mismatch, three_prime)
+        out = [np.empty(len(pr), np.uint32) for _ in range(6)]
+        c = (c_u64 * 8)()
+        ms = (ctypes.c_double * 3)()
+        h, wh = c_vp(), c_vp()
+        check(lib.sw_batch_infix_windows(self._h, _ptr(offs), blob, c_u64(nq), _ptr(pr), c_u64(len(pr)), _ptr(lab), c_u64(ng), c_u64(int(max_dist_permille)),
+                                         _ptr(lens), c_u64(len(lens)), c_u64(mm), c_u64(c3), *[_ptr(a) for a in out], ctypes.byref(h), ctypes.byref(wh), c, ms))
+        res = (Windows(wh, offs), Pileup(h, offs), tuple(out))
+        if stats:
+            d = dict(zip(_ALIGN_COUNTERS, (int(x) for x in c)))
+            d.update(distance_ms=ms[0], store_ms=ms[1], walk_ms=ms[2])
+            res += (d,)
+        return res
+
     def local_alignments(self, queries, pairs, scoring=(2, -3, 5, 2), stats: bool = False) -> dict:
         """The optimal LOCAL alignment of every pair of :meth:`infix_distances` under the scoring system ``(reward, penalty, gapopen,
         gapextend)`` -- a gap of L columns costs ``gapopen + L * gapextend``; the default is blastn's (csrc/local.hip, DESIGN.md section
@@ -221,7 +247,8 @@ class Batch:
         return res
 
     def best_hits(self, queries, kmerlen: int, align: bool = False, loci: bool = False, min_seeds: int = 1, seed_copies=None, local: bool = False,
-                  scoring=(2, -3, 5, 2), pileup=None, n_groups=None, max_dist_permille: int = 1000) -> "BestHits":
+                  scoring=(2, -3, 5, 2), pileup=None, n_groups=None, max_dist_permille: int = 1000, window_lengths=None, window_mismatch: int = 2,
+                  window_three_prime: int = 3) -> "BestHits":
         """For every query (a list of ``str`` or ``bytes``) and every assembly: the best seeded locus and the exact infix edit
         distance of the query to the best substring there (csrc/hits.hip).  A seed is a canonical
         ``kmerlen``-mer that exactly one window of ALL the query text has and that is not its own reverse complement: a query whose
@@ -250,7 +277,14 @@ class Batch:
         ``pileup=groups`` (it implies ``align=True``, combines with everything above and changes none of it)
         piles every winner's canonical alignment into the group of its assembly -- one label per assembly, 0 .. ``n_groups - 1`` or 255
         to leave the assembly out, ``n_groups`` and ``max_dist_permille`` as :meth:`infix_pileup` takes them: the result then answers
-        ``pileup()``, a :class:`Pileup` of base counts per query position and group.  The loci of ``loci=True`` are not piled."""
+        ``pileup()``, a :class:`Pileup` of base counts per query position and group.  The loci of ``loci=True`` are not piled.
+        ``window_lengths=(18, 20, 22, 25)`` (it needs ``pileup=groups``, else ValueError, and changes nothing the
+        call answers without it) also classes every window of those lengths of every query by how the piled winners match it jointly
+        -- 0, 1, 2, 3 or more mismatches, or a gap, and whether it serves as a forward or a reverse oligo with at most
+        ``window_mismatch`` mismatches and none in the ``window_three_prime`` bases at the 3' end: the result then answers ``windows()``,
+        a :class:`Windows`.  The arguments are :meth:`infix_windows`'.  Not BLAST and no thermodynamic model."""
+        if window_lengths is not None and pileup is None:
+            raise ValueError("window_lengths needs pileup=groups: the windows count the pairs the pileup piles")
         offs, blob, nq = _query_csr(queries)
         h = c_vp()
         if loci and int(min_seeds) < 1:
@@ -260,6 +294,14 @@ class Batch:
                 raise ValueError(f"seed_copies must lie in 1..256 (got {seed_copies})")
             lab, ng = _pile_groups(pileup, self.info()["n_assemblies"], n_groups, "assembly")
             ph = c_vp()
+            if window_lengths is not None:
+                lens, mm, c3 = _window_args(window_lengths, window_mismatch, window_three_prime)
+                wh = c_vp()
+                check(lib.sw_batch_best_hits_windows(self._h, _ptr(offs), blob, c_u64(nq), c_u64(int(kmerlen)), c_u64(int(seed_copies or 0)),
+                                                     c_u64(2 if loci else 1), c_u64(int(min_seeds) if loci else 0), _scoring(scoring) if local else None,
+                                                     _ptr(lab), c_u64(ng), c_u64(int(max_dist_permille)), _ptr(lens), c_u64(len(lens)), c_u64(mm), c_u64(c3),
+                                                     ctypes.byref(h), ctypes.byref(ph), ctypes.byref(wh)))
+                return BestHits(h, aligned=True, loci=bool(loci), local=bool(local), pileup=Pileup(ph, offs), windows=Windows(wh, offs))
             check(lib.sw_batch_best_hits_pileup(self._h, _ptr(offs), blob, c_u64(nq), c_u64(int(kmerlen)), c_u64(int(seed_copies or 0)), c_u64(2 if loci else 1),
                                                 c_u64(int(min_seeds) if loci else 0), _scoring(scoring) if local else None, _ptr(lab), c_u64(ng),
                                                 c_u64(int(max_dist_permille)), ctypes.byref(h), ctypes.byref(ph)))
@@ -373,6 +415,29 @@ def _pile_groups(groups, n: int, n_groups, what: str):
         kept = a[a != PILE_LEAVE_OUT]
         n_groups = int(kept.max()) + 1 if len(kept) else 1
     return np.ascontiguousarray(a.astype(np.uint8)), int(n_groups)
+
+
+WINDOW_CLASSES = ("MM0", "MM1", "MM2", "MM3", "MM4P", "GAPPED", "FWD_OK", "REV_OK")   # the last axis of a window table
+
+
+def _window_args(lengths, max_mismatch, three_prime):
+    """(lengths uint32[n], max_mismatch, three_prime) of a windows call, checked as the library checks them."""
+    try:
+        lens = [int(x) for x in lengths]
+    except TypeError:
+        raise ValueError(f"window lengths are 1..8 distinct integers in 8..32 (got {lengths!r})") from None
+    if not 1 <= len(lens) <= 8:
+        raise ValueError(f"the windows take 1..8 lengths (got {len(lens)})")
+    if any(not 8 <= x <= 32 for x in lens):
+        raise ValueError(f"a window length lies outside 8..32 (got {lens})")
+    if len(set(lens)) != len(lens):
+        raise ValueError(f"a window length is given twice (got {lens})")
+    mm, c3 = int(max_mismatch), int(three_prime)
+    if not 0 <= mm <= 8 or mm >= min(lens):
+        raise ValueError(f"max_mismatch must lie in 0..8 and below the shortest window length {min(lens)} (got {max_mismatch})")
+    if not 0 <= c3 <= 8:
+        raise ValueError(f"three_prime must lie in 0..8 (got {three_prime})")
+    return np.array(lens, np.uint32), mm, c3
 
 
 LOCAL_FIELDS = ("score", "qstart", "qend", "sstart", "send", "nident", "mismatch", "gapopen", "gaps")
@@ -776,19 +841,22 @@ class Markers:
         return batch.screen([blob[o[i]:o[i + 1]] for i in range(len(o) - 1)], kmerlen)
 
     def best_hits(self, batch: "Batch", kmerlen: int, select=None, align: bool = False, loci: bool = False, min_seeds: int = 1,
-                  seed_copies=None, local: bool = False, scoring=(2, -3, 5, 2), pileup=None, n_groups=None, max_dist_permille: int = 1000) -> "BestHits":
+                  seed_copies=None, local: bool = False, scoring=(2, -3, 5, 2), pileup=None, n_groups=None, max_dist_permille: int = 1000,
+                  window_lengths=None, window_mismatch: int = 2, window_three_prime: int = 3) -> "BestHits":
         """:meth:`Batch.best_hits` of the representatives' text -- ``sequences(batch, "reps", select)``, in that order -- against
         every assembly of ``batch``.  ``kmerlen`` is the caller's choice; it need not be the graph's k.  ``seed_copies`` is that
         call's: ``None`` keeps a k-mer as a seed only if one window of all representatives has it, ``c`` in 1..256 lets up to c
         windows share it (representatives that overlap or repeat keep their k-mers) and drops a k-mer with more windows whole.
         ``local`` and ``scoring`` are that call's too: the local alignment of every winner (and locus) with affine gap scores; so
         are ``pileup``, ``n_groups`` and ``max_dist_permille``: the winners' base counts per position of every representative, by
-        group of assembly."""
+        group of assembly; and ``window_lengths``, ``window_mismatch`` and ``window_three_prime``: the joint mismatch classes of every
+        window of every representative (it needs ``pileup``)."""
         offs, blob, _ = self.sequences(batch, "reps", select)
         o = offs.astype(np.int64)
         return batch.best_hits([blob[o[i]:o[i + 1]] for i in range(len(o) - 1)], kmerlen, align=align, loci=loci, min_seeds=min_seeds,
                                seed_copies=seed_copies, local=local, scoring=scoring, pileup=pileup, n_groups=n_groups,
-                               max_dist_permille=max_dist_permille)
+                               max_dist_permille=max_dist_permille, window_lengths=window_lengths, window_mismatch=window_mismatch,
+                               window_three_prime=window_three_prime)
 
     def candidates(self, min_len: int) -> np.ndarray:
         """Indices of the subgraphs the reference keeps (markers.py:514-517): len >= min_len, neither single nor dup."""
@@ -1133,6 +1201,9 @@ class Pileup:
         return out
 
     def stats(self) -> dict:
+        """The call's counters and ``pile_walk_ms``, the time of the walk that filled the table.  In a call with windows one walk
+        fills both tables: ``pile_walk_ms`` is then that walk's time, the same figure as ``Windows.stats()["window_walk_ms"]``, and
+        not what the pileup alone would have taken."""
         c = (c_u64 * 5)()
         ms = (ctypes.c_double * 1)()
         check(lib.sw_pileup_stats(self._h, c, ms))
@@ -1143,6 +1214,71 @@ class Pileup:
     def close(self) -> None:
         if self._h:
             lib.sw_pileup_free(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Windows:
+    """Joint mismatch classes per query window, window length and group over the canonical alignments of a call's piled pairs,
+    resident on the device (:meth:`Batch.infix_windows`, ``Batch.best_hits(pileup=..., window_lengths=...)``; csrc/align.hip, DESIGN.md
+    section 3.2l).  A row is a window's start in the query; rows whose window would pass the query's end stay 0.  The last axis is
+    WINDOW_CLASSES: ``MM0`` .. ``MM3`` count the pairs whose copy faces the whole window without a gap and with exactly 0..3
+    mismatches, ``MM4P`` with 4 or more, ``GAPPED`` with an indel inside the window -- these six add up to the pileup's depth;
+    ``FWD_OK`` / ``REV_OK`` count the ungapped pairs with at most ``max_mismatch`` mismatches and none in the ``three_prime`` bases at
+    the 3' end of the window itself / of its reverse complement as an oligo.  Exact integers.  Not BLAST, no Tm, no dG."""
+
+    def __init__(self, handle: c_vp, offsets: np.ndarray):
+        self._h = handle
+        self._offs = np.array(offsets, np.uint64)
+
+    def sizes(self):
+        """(queries, bases of all queries, groups, lengths, max_mismatch, three_prime)"""
+        v = [c_u64() for _ in range(6)]
+        check(lib.sw_windows_sizes(self._h, *[ctypes.byref(x) for x in v]))
+        return tuple(x.value for x in v)
+
+    @property
+    def lengths(self) -> tuple:
+        """The window lengths, in the order the call gave them: the table's second axis."""
+        out = np.zeros(self.sizes()[3], np.uint32)
+        check(lib.sw_windows_lengths(self._h, _ptr(out)))
+        return tuple(int(x) for x in out)
+
+    def _rows(self, q0: int, q1: int) -> np.ndarray:
+        _, _, ng, nl, _, _ = self.sizes()
+        out = np.empty((int(self._offs[q1] - self._offs[q0]), nl, ng, len(WINDOW_CLASSES)), np.uint32)
+        check(lib.sw_windows_export(self._h, c_u64(q0), c_u64(q1), _ptr(out) if out.size else None))
+        return out
+
+    def counts(self, q: int) -> np.ndarray:
+        """uint32[len(query q), lengths, groups, 8]"""
+        q = int(q)
+        if not 0 <= q < len(self._offs) - 1:
+            raise ValueError(f"query {q} is none of the call's {len(self._offs) - 1}")
+        return self._rows(q, q + 1)
+
+    def table(self):
+        """``(offsets, uint32[total, lengths, groups, 8])``: the rows of query q are ``[offsets[q], offsets[q + 1])``."""
+        return self._offs.copy(), self._rows(0, len(self._offs) - 1)
+
+    def stats(self) -> dict:
+        """Windows visited, adds issued, table bytes; ``window_walk_ms`` is the one walk that fills this table and the pileup's,
+        ``finish_ms`` the finishing pass."""
+        c = (c_u64 * 3)()
+        ms = (ctypes.c_double * 2)()
+        check(lib.sw_windows_stats(self._h, c, ms))
+        d = dict(zip(("windows", "adds", "table_bytes"), (int(x) for x in c)))
+        d.update(window_walk_ms=ms[0], finish_ms=ms[1])
+        return d
+
+    def close(self) -> None:
+        if self._h:
+            lib.sw_windows_free(self._h)
             self._h = None
 
     def __del__(self):
@@ -1166,14 +1302,23 @@ class BestHits:
     optimal local alignment of every hit on its window under an affine scoring system (csrc/local.hip; still
     not BLAST): ``score``, ``qstart``, ``qend``, ``sstart``, ``send``, ``local_nident``, ``local_mismatch``, ``local_gapopen`` and
     ``local_gaps``, NO_HIT where there is no hit.  Made with ``pileup=groups`` it also holds the :class:`Pileup` of the winners'
-    canonical alignments by group of assembly: ``pileup()``."""
+    canonical alignments by group of assembly: ``pileup()``; made with ``window_lengths`` too, the
+    :class:`Windows` of the same winners: ``windows()``."""
 
-    def __init__(self, handle: c_vp, aligned: bool = False, loci: bool = False, local: bool = False, pileup: "Pileup | None" = None):
+    def __init__(self, handle: c_vp, aligned: bool = False, loci: bool = False, local: bool = False, pileup: "Pileup | None" = None,
+                 windows: "Windows | None" = None):
         self._h = handle
         self._aligned = aligned
         self._loci = loci
         self._local = local
         self._pileup = pileup
+        self._windows = windows
+
+    def windows(self) -> "Windows":
+        """The :class:`Windows` of the winners; it is closed with these hits."""
+        if self._windows is None:
+            raise ValueError("these best hits were made without window_lengths")
+        return self._windows
 
     def pileup(self) -> "Pileup":
         """The :class:`Pileup` of the winners; it is closed with these hits."""
@@ -1393,6 +1538,8 @@ class BestHits:
     def close(self) -> None:
         if self._pileup is not None:
             self._pileup.close()
+        if self._windows is not None:
+            self._windows.close()
         if self._h:
             lib.sw_hits_free(self._h)
             self._h = None
