@@ -474,6 +474,31 @@ int sw_screen_stats(const sw_screen *h, uint64_t *counters, double *ms);
 int sw_screen_chunk_ms(const sw_screen *h, double *probe_ms, double *reduce_ms);
 void sw_screen_free(sw_screen *h);
 
+/* ---- k-mer profile: per position of the query text, in how many assemblies of every group the k-mer that starts there occurs
+ * ANYWHERE, and how many copies the group holds (csrc/screen.hip; DESIGN.md section 3.2m is the specification,
+ * tests/tools/kprofile_host.py restates it).  None of this has a counterpart in the reference; it is NOT BLAST and fills none of
+ * MarkerMetrics.  Queries, alphabet, k, windows and canonical words are sw_batch_screen's; the groups are the pileup's: one label per
+ * assembly, 0 .. n_groups - 1 with n_groups in 1..8, 255 leaves the assembly out.  Row p of the tables is byte p of the query text
+ * (offsets[q] + u).  present[p][g] = the assemblies labelled g that hold the canonical k-mer of the window starting at p in at least
+ * one valid window; copies[p][g] = the valid windows of those assemblies whose canonical word equals it (a window counts once,
+ * whatever its strand).  A row where no window starts -- the last k - 1 bytes of a query, a window with an invalid byte, a query
+ * shorter than k -- reads all ones in both tables, in every group. */
+/* (no counterpart in the reference)  sw_batch_screen plus the profile: *out answers everything sw_batch_screen's result answers, bit
+ * for bit, and the profile getters below.  copies != 0 also counts the copies.  n_groups outside 1..8 or a label in
+ * n_groups .. 254 -> SW_ERR_VALUE before a device is touched.  A single-device call on a resident batch. */
+int sw_batch_screen_profile(const sw_batch *batch, const uint64_t *offsets, const char *blob, uint64_t n_queries, uint64_t k,
+                            const uint8_t *labels, uint64_t n_groups, int copies, void *stream, sw_screen **out);
+/* (no counterpart in the reference)  Rows (the bytes of the query text), groups, whether copies were counted (any pointer may be
+ * NULL).  This and the three getters below: SW_ERR_VALUE for a screen made by sw_batch_screen. */
+int sw_screen_profile_sizes(const sw_screen *h, uint64_t *rows, uint64_t *n_groups, uint64_t *has_copies);
+/* (no counterpart in the reference)  D2H copy: present[rows * n_groups], copies[rows * n_groups] (NULL: not wanted; SW_ERR_VALUE
+ * if they were not counted), group_sizes[n_groups] = the assemblies of every label (any pointer may be NULL). */
+int sw_screen_profile_export(const sw_screen *h, uint32_t *present, uint64_t *copies, uint32_t *group_sizes);
+/* (no counterpart in the reference)  counters[2] = { bytes of the profile's device tables (per k-mer, per position and the map
+ * between them), copy adds issued by the probe }; ms[2] = { the transposed reduction k_scr_profile summed over the chunks, the
+ * gather } (HIP events).  With a profile, sw_screen_stats' reduce time does not contain the transposed reduction. */
+int sw_screen_profile_stats(const sw_screen *h, uint64_t *counters, double *ms);
+
 /* ---- the best hit of every query in every assembly: seed vote + infix edit distance (csrc/hits.hip) ------------------------------
  * Covers the ground of markers.eval_markers' output (src/seqwin/markers.py:531-604 keeps the best BLAST hit's nident, mismatch and
  * gaps per (query, assembly)) with an exactly specified quantity of its own.  There is no counterpart in the reference: this is NOT

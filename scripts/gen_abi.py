@@ -37,6 +37,15 @@ def ctype_of(decl: str) -> str:
     return "c_void_p"
 
 
+NO_COUNTERPART = "(no counterpart in the reference)"
+
+
+def no_counterpart() -> set:
+    """The entry points whose own comment in the header opens with NO_COUNTERPART: the table says so too."""
+    pat = r"/\*\s*" + re.escape(NO_COUNTERPART) + r"(?:[^*]|\*(?!/))*\*/\s*[A-Za-z_][A-Za-z0-9_ \*]*?\b(sw_[a-z0-9_]+)\s*\("
+    return set(re.findall(pat, HEADER.read_text()))
+
+
 def parse():
     text = HEADER.read_text()
     text = re.sub(r"/\*.*?\*/", " ", text, flags=re.S)
@@ -60,9 +69,10 @@ def render(protos) -> str:
              "from ctypes import (CFUNCTYPE, POINTER, c_char_p, c_double, c_float, c_int, c_int64, c_size_t, c_uint, c_uint32, c_uint64,  # noqa: F401",
              "                    c_void_p)", "",
              "LOG_FN = CFUNCTYPE(None, c_char_p, c_char_p)   # sw_log_fn", "", "PROTOTYPES = {"]
+    own = no_counterpart()
     for name in sorted(protos):
         res, argl = protos[name]
-        lines.append(f'    "{name}": ({res}, [{", ".join(argl)}]),')
+        lines.append(f'    "{name}": ({res}, [{", ".join(argl)}]),' + (f"   # {NO_COUNTERPART}" if name in own else ""))
     lines += ["}", ""]
     return "\n".join(lines)
 

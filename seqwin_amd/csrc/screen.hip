@@ -17,6 +17,13 @@
 //                  atomicOr -- consecutive hits that fall into one bitmap word leave as one atomic
 //   k_scr_reduce   counts[q, a] = sum over q's pairs of popcount(bitmap[a][word] & mask): a wave per (query, assembly)
 // The bitmap holds a chunk of assemblies (a budget, 1 GiB by default); tiles are ordered by assembly, so a chunk is a tile range.
+//
+// The k-mer profile (sw_batch_screen_profile; DESIGN.md section 3.2m, tests/tools/kprofile_host.py restates it) reduces the same bitmap
+// the other way -- per distinct k-mer and group of assemblies, the rows that hold it -- and reads the result out per text position:
+//   k_scr_profile  per chunk, behind k_scr_reduce: bit-sliced vertical counters per lane, a lane per bitmap word, rows in group order
+//   k_scr_probe<true>   the probe with one 64-bit atomicAdd per hit into the copies table (only with copies)
+//   k_scr_posnum / k_scr_gather   the position -> number map of the query side kept, the tables per number gathered per position
+// A screen without a profile launches none of these.
 #include "screen_core.hpp"
 
 namespace sw {
@@ -33,7 +40,16 @@ struct ProbeArgs {
     uint32_t k;
 };
 
-__global__ __launch_bounds__(SCR_TPB) void k_scr_probe(ProbeArgs g)
+// what the probe with copy counts (the k-mer profile) takes on top
+struct ProbeCopyArgs : ProbeArgs {
+    const uint8_t *labels;           // [n_asm] the group of every assembly, 255: left out
+    unsigned long long *copies;      // [distinct][n_groups]
+    uint32_t n_groups;
+};
+
+// COPIES = false is the screen's probe as it always was (every addition below sits behind `if constexpr (COPIES)`); true: a hit also
+// adds one to copies[number][group of the assembly] (stat[2]: those adds)
+template <bool COPIES> __global__ __launch_bounds__(SCR_TPB) void k_scr_probe(std::conditional_t<COPIES, ProbeCopyArgs, ProbeArgs> g)
 {
     const uint32_t lane = threadIdx.x % SCR_WAVE;
     uint32_t r, n_mine;
@@ -41,6 +57,9 @@ __global__ __launch_bounds__(SCR_TPB) void k_scr_probe(ProbeArgs g)
     if (!wave_tile(g.v, lane, r, first, n_mine)) return;   // (the whole wave)
     const uint32_t a = g.v.run_asm[r], k = g.k;
     unsigned long long hits = 0, atomics = 0;
+    [[maybe_unused]] uint32_t label = 0xFFu;   // (uniform in the wave: a tile lies in one assembly)
+    [[maybe_unused]] unsigned long long adds = 0;
+    if constexpr (COPIES) label = g.labels[a];
     KmerRoller R(g.v.packed, k);
     if (n_mine) {
         R.start(g.v.run_base[r] + first);
@@ -68,6 +87,12 @@ __global__ __launch_bounds__(SCR_TPB) void k_scr_probe(ProbeArgs g)
             const uint32_t id = scr_find_from(g.t, canon[j], home[j], slot[j]);
             if (id == SCR_NONE) continue;
             ++hits;
+            if constexpr (COPIES) {
+                if (label != 0xFFu) {
+                    atomicAdd(g.copies + (uint64_t)id * g.n_groups + label, 1ull);
+                    ++adds;
+                }
+            }
             if ((id >> 5) != cur_word) {   // consecutive hits in one bitmap word leave as one atomic
                 if (cur_mask) {
                     atomicOr(row + cur_word, cur_mask);
@@ -88,6 +113,102 @@ __global__ __launch_bounds__(SCR_TPB) void k_scr_probe(ProbeArgs g)
     if (lane == 0 && hits) {
         atomicAdd(g.stat, hits);
         atomicAdd(g.stat + 1, atomics);
+    }
+    if constexpr (COPIES) {
+        adds = wave_sum(adds);
+        if (lane == 0 && adds) atomicAdd(g.stat + 2, adds);
+    }
+}
+
+// ---- the k-mer profile: the bitmap reduced the other way ------------------------------------------------
+constexpr uint32_t PRF_PLANES = 8;                          // bit-sliced counter planes of a lane: one count per bit of its bitmap word
+constexpr uint32_t PRF_FLUSH = (1u << PRF_PLANES) - 1;      // rows the planes take before they are emptied into the lane's 32 counts
+constexpr uint32_t PRF_SLICE = 1024;                        // rows of a chunk (in group order) per workgroup; chosen without a measurement
+constexpr uint32_t PRF_MAX_GROUPS = 8;
+
+// the planes' 32 counts added to acc, the planes emptied
+__device__ __forceinline__ void prf_flush(uint32_t (&plane)[PRF_PLANES], uint32_t (&acc)[32])
+{
+#pragma unroll
+    for (uint32_t b = 0; b < 32; ++b) {
+        uint32_t c = 0;
+#pragma unroll
+        for (uint32_t p = 0; p < PRF_PLANES; ++p) c |= ((plane[p] >> b) & 1u) << p;
+        acc[b] += c;
+    }
+#pragma unroll
+    for (uint32_t p = 0; p < PRF_PLANES; ++p) plane[p] = 0;
+}
+
+// present[number][group] += the rows of the group whose bit `number` is set.  A workgroup takes SCR_TPB consecutive bitmap words -- a
+// lane one word of every row, so a wave reads 64 consecutive words of a row -- and a slice of at most PRF_SLICE of the chunk's kept
+// rows, which the host has put in group order (order[] / olabel[]: the row in the chunk and its group): the group is uniform and
+// changes at most n_groups - 1 times in a slice.  A row's word is added to the lane's planes by a ripple of half adders; the planes
+// are emptied into 32 counts every PRF_FLUSH rows, the counts leave once per (word tile, slice, group), one atomicAdd per non-zero count.
+__global__ __launch_bounds__(SCR_TPB) void k_scr_profile(const uint32_t *__restrict__ bitmap, uint64_t words, uint64_t n_distinct,
+                                                         const uint32_t *__restrict__ order, const uint8_t *__restrict__ olabel, uint32_t n_kept,
+                                                         uint32_t n_groups, uint64_t block0, uint32_t slices, uint32_t *__restrict__ present)
+{
+    const uint64_t blk = block0 + blockIdx.x;
+    const uint64_t w = (blk / slices) * SCR_TPB + threadIdx.x;
+    const uint32_t i0 = (uint32_t)(blk % slices) * PRF_SLICE, i1 = i0 + PRF_SLICE < n_kept ? i0 + PRF_SLICE : n_kept;
+    if (i0 >= i1) return;   // (the whole workgroup; the host launches no such slice)
+    const bool mine = w < words;
+    uint32_t plane[PRF_PLANES], acc[32];
+#pragma unroll
+    for (uint32_t p = 0; p < PRF_PLANES; ++p) plane[p] = 0;
+#pragma unroll
+    for (uint32_t b = 0; b < 32; ++b) acc[b] = 0;
+    uint32_t in_planes = 0, group = olabel[i0];
+    for (uint32_t i = i0; i <= i1; ++i) {   // (i == i1: the last group leaves)
+        const uint32_t gi = i < i1 ? olabel[i] : 0xFFFFFFFFu;
+        if (gi != group) {
+            prf_flush(plane, acc);
+            in_planes = 0;
+            if (mine) {
+#pragma unroll
+                for (uint32_t b = 0; b < 32; ++b) {
+                    const uint64_t number = w * 32 + b;
+                    if (acc[b] && number < n_distinct) atomicAdd(present + number * n_groups + group, acc[b]);
+                    acc[b] = 0;
+                }
+            }
+            group = gi;
+            if (i == i1) break;
+        } else if (in_planes == PRF_FLUSH) {
+            prf_flush(plane, acc);
+            in_planes = 0;
+        }
+        uint32_t carry = mine ? bitmap[(uint64_t)order[i] * words + w] : 0u;
+#pragma unroll
+        for (uint32_t p = 0; p < PRF_PLANES; ++p) {
+            const uint32_t t = plane[p] & carry;
+            plane[p] ^= carry;
+            carry = t;
+        }
+        ++in_planes;
+    }
+}
+
+// pnum[text position] = the number of the distinct word whose window starts there (pnum is SCR_NONE everywhere else)
+__global__ __launch_bounds__(SCR_TPB) void k_scr_posnum(uint64_t base, uint64_t end, const uint32_t *__restrict__ vpos, const uint32_t *__restrict__ sidx,
+                                                        const uint32_t *__restrict__ number, uint32_t *__restrict__ pnum)
+{
+    const uint64_t j = base + (uint64_t)blockIdx.x * SCR_TPB + threadIdx.x;
+    if (j < end) pnum[vpos[j]] = number[sidx[j]];
+}
+
+// the per-number tables read out per text position; a position where no window starts gets all ones.  copies / out_copies may be null
+__global__ __launch_bounds__(SCR_TPB) void k_scr_gather(uint64_t base, uint64_t end, const uint32_t *__restrict__ pnum, uint32_t n_groups,
+                                                        const uint32_t *__restrict__ present, const unsigned long long *__restrict__ copies,
+                                                        uint32_t *__restrict__ out_present, unsigned long long *__restrict__ out_copies)
+{
+    const uint64_t p = base + (uint64_t)blockIdx.x * SCR_TPB + threadIdx.x;
+    if (p >= end) return;
+    const uint32_t num = pnum[p];
+    for (uint32_t g = 0; g < n_groups; ++g) {
+        out_present[p * n_groups + g] = num == SCR_NONE ? 0xFFFFFFFFu : present[(uint64_t)num * n_groups + g];
+        if (out_copies) out_copies[p * n_groups + g] = num == SCR_NONE ? ~0ull : copies[(uint64_t)num * n_groups + g];
     }
 }
 
@@ -121,12 +242,28 @@ struct sw_screen {
     uint64_t counters[10] = {};            // sw_screen_stats
     double ms[3] = {};                     // table build, probe, reduce
     std::vector<double> chunk_probe_ms, chunk_reduce_ms;
+    // the k-mer profile of sw_batch_screen_profile; none of it exists in a plain screen
+    bool profiled = false, has_copies = false;
+    uint64_t prof_rows = 0, prof_groups = 0;             // rows: the bytes of the query text
+    sw::DevArray<uint32_t> present;                      // [prof_rows][prof_groups]
+    sw::DevArray<unsigned long long> copies;             // [prof_rows][prof_groups], with has_copies
+    std::vector<uint32_t> group_sizes;                   // [prof_groups]
+    uint64_t prof_counters[2] = {};                      // table bytes, copy adds issued
+    double prof_ms[2] = {};                              // k_scr_profile, k_scr_gather
 };
 
 namespace sw {
 namespace {
 
-void batch_screen(const sw_batch &b, const uint64_t *offsets, const char *blob, uint64_t nq, uint32_t k, hipStream_t stream, sw_screen &o)
+struct ProfileCall {
+    const uint8_t *labels;   // [n_asm]
+    uint32_t n_groups;
+    bool copies;
+};
+
+// pc: null for the plain screen, which then launches what it always launched
+void batch_screen(const sw_batch &b, const uint64_t *offsets, const char *blob, uint64_t nq, uint32_t k, hipStream_t stream, sw_screen &o,
+                  const ProfileCall *pc = nullptr)
 {
     const HostBatch &h = b.host;
     const uint64_t n_asm = h.n_assemblies, text_bytes = nq ? offsets[nq] : 0;
@@ -175,6 +312,29 @@ void batch_screen(const sw_batch &b, const uint64_t *offsets, const char *blob, 
         for (uint64_t q = 0; q < nq; ++q) pair_off_host[q + 1] = pair_off_host[q] + np[q];
         if (pair_off_host[nq] != n_pairs) raise(SW_ERR_RUNTIME, "internal error: the queries' pair lists do not add up");
     }
+    // the profile keeps the position -> number map of the query side, and the tables per number the chunks add to
+    const uint32_t ng = pc ? pc->n_groups : 0;
+    DevArray<uint32_t> pnum, dpresent;
+    DevArray<unsigned long long> dcopies;
+    if (pc) {
+        o.profiled = true;
+        o.has_copies = pc->copies;
+        o.prof_rows = text_bytes;
+        o.prof_groups = ng;
+        o.group_sizes.assign(ng, 0);
+        for (uint64_t a = 0; a < n_asm; ++a)
+            if (pc->labels[a] != 0xFF) ++o.group_sizes[pc->labels[a]];
+        pnum.alloc(text_bytes);
+        dpresent.alloc(n_distinct * ng);
+        if (text_bytes) SW_HIP(hipMemsetAsync(pnum.p, 0xFF, text_bytes * 4, stream));
+        if (n_distinct) SW_HIP(hipMemsetAsync(dpresent.p, 0, n_distinct * ng * 4, stream));
+        if (pc->copies) {
+            dcopies.alloc(n_distinct * ng);
+            if (n_distinct) SW_HIP(hipMemsetAsync(dcopies.p, 0, n_distinct * ng * 8, stream));
+        }
+        if (n_valid)
+            launch_1d(k_scr_posnum, n_valid, stream, (const uint32_t *)Q.vpos.p, (const uint32_t *)Q.sidx.p, (const uint32_t *)Q.number.p, pnum.p);
+    }
     Q.release_temporaries();
     DevArray<uint32_t> &slots = Q.slots;
     DevArray<uint64_t> &by_number = Q.by_number;
@@ -191,7 +351,7 @@ void batch_screen(const sw_batch &b, const uint64_t *offsets, const char *blob, 
     // ---- probe and reduce, a chunk of assemblies at a time ----
     uint64_t probed = 0, launches = 0, chunks = 0;
     unsigned long long stat[2] = {};
-    std::vector<std::unique_ptr<Event>> ev;
+    std::vector<std::unique_ptr<Event>> ev, pev;
     if (n_distinct && n_asm && nq) {
         const uint64_t words = (n_distinct + 31) / 32;
         // the bitmap's budget changes speed only; 1 GiB has no measurement behind it.  SEQWIN_AMD_SCR_BITMAP_KB (test library) sets it
@@ -200,8 +360,8 @@ void batch_screen(const sw_batch &b, const uint64_t *offsets, const char *blob, 
         const uint64_t rows_max = std::min<uint64_t>(std::max<uint64_t>(budget / (words * 4), 1), n_asm);
         DevArray<uint32_t> bitmap(rows_max * words);
         DevRunTiles runs(T, b.d_packed.p, stream);
-        DevArray<unsigned long long> d_stat(2);
-        SW_HIP(hipMemsetAsync(d_stat.p, 0, 16, stream));
+        DevArray<unsigned long long> d_stat(3);
+        SW_HIP(hipMemsetAsync(d_stat.p, 0, 24, stream));
         SW_HIP(hipMemsetAsync(bitmap.p, 0, rows_max * words * 4, stream));
         ProbeArgs g{};
         g.t = Table{slots.p, by_number.p, cap, bits};
@@ -211,13 +371,50 @@ void batch_screen(const sw_batch &b, const uint64_t *offsets, const char *blob, 
         g.k = k;
         const uint32_t blocks_max = launch_blocks(SCR_BLOCKS_ENV);
         const uint32_t q_step = (uint32_t)std::max<uint64_t>(blocks_max / ((rows_max + SCR_RED_ROWS - 1) / SCR_RED_ROWS), 1);
+        // the profile's rows: every chunk's kept rows in group order (a stable sort: a counting pass per chunk), at the chunk's place
+        ProbeCopyArgs gc{};
+        std::vector<uint32_t> kept_of_chunk;
+        DevArray<uint32_t> d_order;
+        DevArray<uint8_t> d_olabel, d_labels;
+        if (pc) {
+            std::vector<uint32_t> order(n_asm);
+            std::vector<uint8_t> olabel(n_asm, 0xFF);
+            for (uint64_t a0 = 0; a0 < n_asm; a0 += rows_max) {
+                const uint64_t a1 = std::min<uint64_t>(n_asm, a0 + rows_max);
+                uint64_t at = a0;
+                for (uint32_t grp = 0; grp < ng; ++grp)
+                    for (uint64_t a = a0; a < a1; ++a)
+                        if (pc->labels[a] == grp) {
+                            order[at] = (uint32_t)(a - a0);
+                            olabel[at++] = (uint8_t)grp;
+                        }
+                kept_of_chunk.push_back((uint32_t)(at - a0));
+            }
+            d_order.alloc(n_asm);
+            d_olabel.alloc(n_asm);
+            up(d_order.p, order.data(), n_asm * 4);
+            up(d_olabel.p, olabel.data(), n_asm);
+            if (pc->copies) {
+                d_labels.alloc(n_asm);
+                up(d_labels.p, pc->labels, n_asm);
+            }
+            SW_HIP(hipStreamSynchronize(stream));   // (order and olabel leave this block)
+        }
         for (uint64_t a0 = 0; a0 < n_asm; a0 += rows_max, ++chunks) {
             const uint64_t a1 = std::min<uint64_t>(n_asm, a0 + rows_max), rows = a1 - a0;
             for (int i = 0; i < 3; ++i) ev.emplace_back(new Event);
             SW_HIP(hipEventRecord(*ev[3 * chunks], stream));
             g.asm0 = (uint32_t)a0;
             g.v = runs.view(asm_tile_off[a0], asm_tile_off[a1]);
-            launches += launch_tiles(k_scr_probe, g, blocks_max, stream);
+            if (pc && pc->copies) {
+                static_cast<ProbeArgs &>(gc) = g;
+                gc.labels = d_labels.p;
+                gc.copies = dcopies.p;
+                gc.n_groups = ng;
+                launches += launch_tiles(k_scr_probe<true>, gc, blocks_max, stream);
+            } else {
+                launches += launch_tiles(k_scr_probe<false>, g, blocks_max, stream);
+            }
             probed += asm_kmers[a1] - asm_kmers[a0];
             SW_HIP(hipEventRecord(*ev[3 * chunks + 1], stream));
             const uint32_t row_tiles = (uint32_t)((rows + SCR_RED_ROWS - 1) / SCR_RED_ROWS);
@@ -228,21 +425,57 @@ void batch_screen(const sw_batch &b, const uint64_t *offsets, const char *blob, 
                                    (const uint32_t *)pmask.p, o.counts.p);
                 SW_HIP(hipGetLastError());
             }
+            if (pc) {   // the same bitmap reduced the other way, before it is cleared
+                for (int i = 0; i < 2; ++i) pev.emplace_back(new Event);
+                SW_HIP(hipEventRecord(*pev[2 * chunks], stream));
+                const uint32_t kept = kept_of_chunk[chunks];
+                const uint32_t slices = (kept + PRF_SLICE - 1) / PRF_SLICE;
+                const uint64_t total = (words + SCR_TPB - 1) / SCR_TPB * slices;
+                for (uint64_t b0 = 0; b0 < total; b0 += blocks_max) {
+                    hipLaunchKernelGGL(k_scr_profile, dim3((unsigned)std::min<uint64_t>(blocks_max, total - b0)), dim3(SCR_TPB), 0, stream,
+                                       (const uint32_t *)bitmap.p, words, n_distinct, (const uint32_t *)d_order.p + a0, (const uint8_t *)d_olabel.p + a0, kept, ng,
+                                       b0, slices, dpresent.p);
+                    SW_HIP(hipGetLastError());
+                }
+                SW_HIP(hipEventRecord(*pev[2 * chunks + 1], stream));
+            }
             if (a1 < n_asm) SW_HIP(hipMemsetAsync(bitmap.p, 0, rows * words * 4, stream));   // (cleared for the next chunk)
             SW_HIP(hipEventRecord(*ev[3 * chunks + 2], stream));
         }
         SW_HIP(hipMemcpyAsync(stat, d_stat.p, 16, hipMemcpyDeviceToHost, stream));
+        if (pc) SW_HIP(hipMemcpyAsync(&o.prof_counters[1], d_stat.p + 2, 8, hipMemcpyDeviceToHost, stream));
         SW_HIP(hipStreamSynchronize(stream));   // (the temporaries go back to the pool behind the kernels)
+    }
+    Event g0, g1;
+    if (pc) {   // the tables per number read out per text position
+        o.present.alloc(text_bytes * ng);
+        if (pc->copies) o.copies.alloc(text_bytes * ng);
+        SW_HIP(hipEventRecord(g0, stream));
+        if (text_bytes)
+            launch_1d(k_scr_gather, text_bytes, stream, (const uint32_t *)pnum.p, ng, (const uint32_t *)dpresent.p, (const unsigned long long *)dcopies.p,
+                      o.present.p, o.copies.p);
+        SW_HIP(hipEventRecord(g1, stream));
+        o.prof_counters[0] = pnum.bytes() + dpresent.bytes() + dcopies.bytes() + o.present.bytes() + o.copies.bytes();
     }
     SW_HIP(hipStreamSynchronize(stream));
     float ms = 0;
     SW_HIP(hipEventElapsedTime(&ms, e0, e1));
     o.ms[0] = ms;
+    if (pc) {
+        SW_HIP(hipEventElapsedTime(&ms, g0, g1));
+        o.prof_ms[1] = ms;
+    }
     for (uint64_t c = 0; c < chunks; ++c) {
         SW_HIP(hipEventElapsedTime(&ms, *ev[3 * c], *ev[3 * c + 1]));
         o.chunk_probe_ms.push_back(ms);
         o.ms[1] += ms;
         SW_HIP(hipEventElapsedTime(&ms, *ev[3 * c + 1], *ev[3 * c + 2]));
+        if (pc) {   // (the profile kernel ran between the two events: its time is its own)
+            float pms = 0;
+            SW_HIP(hipEventElapsedTime(&pms, *pev[2 * c], *pev[2 * c + 1]));
+            o.prof_ms[0] += pms;
+            ms = ms > pms ? ms - pms : 0;
+        }
         o.chunk_reduce_ms.push_back(ms);
         o.ms[2] += ms;
     }
@@ -254,6 +487,14 @@ void batch_screen(const sw_batch &b, const uint64_t *offsets, const char *blob, 
 }  // namespace sw
 
 using namespace sw;
+
+// the screen behind a profile getter; a screen made without a profile answers none of them
+static const sw_screen &profiled(const sw_screen *h)
+{
+    if (!h) raise(SW_ERR_VALUE, "screen: a NULL handle");
+    if (!h->profiled) raise(SW_ERR_VALUE, "screen: this screen was made without a profile (sw_batch_screen_profile makes one)");
+    return *h;
+}
 
 extern "C" {
 
@@ -269,6 +510,64 @@ int sw_batch_screen(const sw_batch *batch, const uint64_t *offsets, const char *
         o->device = batch->device;
         batch_screen(*batch, offsets, blob, n_queries, (uint32_t)k, (hipStream_t)stream, *o);
         *out = o.release();
+    });
+}
+
+int sw_batch_screen_profile(const sw_batch *batch, const uint64_t *offsets, const char *blob, uint64_t n_queries, uint64_t k, const uint8_t *labels,
+                            uint64_t n_groups, int copies, void *stream, sw_screen **out)
+{
+    return guarded([&] {
+        if (k < 1 || k > 32) raise(SW_ERR_VALUE, "screen: k-mer length must lie in 1..32 (got %llu)", (unsigned long long)k);
+        if (!batch || !out) raise(SW_ERR_VALUE, "screen: a NULL handle or array");
+        check_queries("screen", offsets, blob, n_queries);
+        if (n_groups < 1 || n_groups > PRF_MAX_GROUPS)
+            raise(SW_ERR_VALUE, "screen: the profile takes 1..%u groups (got %llu)", PRF_MAX_GROUPS, (unsigned long long)n_groups);
+        const uint64_t n_asm = batch->host.n_assemblies;
+        if (n_asm && !labels) raise(SW_ERR_VALUE, "screen: a NULL handle or array");
+        for (uint64_t a = 0; a < n_asm; ++a)
+            if (labels[a] != 0xFF && labels[a] >= n_groups)
+                raise(SW_ERR_VALUE, "screen: the group label %u of assembly %llu is neither below the %llu groups nor 255", (unsigned)labels[a],
+                      (unsigned long long)a, (unsigned long long)n_groups);
+        require_device(batch->device, "the batch");
+        StreamScope scope((hipStream_t)stream);
+        std::unique_ptr<sw_screen> o(new sw_screen);
+        o->device = batch->device;
+        const ProfileCall pc{labels, (uint32_t)n_groups, copies != 0};
+        batch_screen(*batch, offsets, blob, n_queries, (uint32_t)k, (hipStream_t)stream, *o, &pc);
+        *out = o.release();
+    });
+}
+
+int sw_screen_profile_sizes(const sw_screen *h, uint64_t *rows, uint64_t *n_groups, uint64_t *has_copies)
+{
+    return guarded([&] {
+        const sw_screen &s = profiled(h);
+        if (rows) *rows = s.prof_rows;
+        if (n_groups) *n_groups = s.prof_groups;
+        if (has_copies) *has_copies = s.has_copies ? 1 : 0;
+    });
+}
+
+int sw_screen_profile_export(const sw_screen *h, uint32_t *present, uint64_t *copies, uint32_t *group_sizes)
+{
+    return guarded([&] {
+        const sw_screen &s = profiled(h);
+        if (copies && !s.has_copies) raise(SW_ERR_VALUE, "screen: this profile was made without copy counts");
+        if (group_sizes) memcpy(group_sizes, s.group_sizes.data(), s.prof_groups * 4);
+        const uint64_t n = s.prof_rows * s.prof_groups;
+        if (!n || (!present && !copies)) return;
+        require_device(s.device, "the screen");
+        if (present) SW_HIP(hipMemcpy(present, s.present.p, n * 4, hipMemcpyDeviceToHost));
+        if (copies) SW_HIP(hipMemcpy(copies, s.copies.p, n * 8, hipMemcpyDeviceToHost));
+    });
+}
+
+int sw_screen_profile_stats(const sw_screen *h, uint64_t *counters, double *ms)
+{
+    return guarded([&] {
+        const sw_screen &s = profiled(h);
+        if (counters) memcpy(counters, s.prof_counters, sizeof s.prof_counters);
+        if (ms) memcpy(ms, s.prof_ms, sizeof s.prof_ms);
     });
 }
 

@@ -121,16 +121,29 @@ class Batch:
                                    ctypes.byref(h)))
         return MinHash(h)
 
-    def screen(self, queries, kmerlen: int, stream: int = 0) -> "Screen":
+    def screen(self, queries, kmerlen: int, profile=None, n_groups=None, copies: bool = False, stream: int = 0) -> "Screen":
         """For every query (a list of ``str`` or ``bytes``) and every assembly: how many of the query's distinct canonical
         ``kmerlen``-mers occur anywhere in the assembly, exactly (csrc/screen.hip).  ACGTU in either case, U
-        reads as T, every other byte ends a window.  Not BLAST.  ValueError for a k-mer length outside 1..32."""
+        reads as T, every other byte ends a window.  Not BLAST.  ValueError for a k-mer length outside 1..32.
+        ``profile=groups`` (it changes nothing the call answers without it) also counts, for every position
+        of every query and every group, the assemblies of the group that hold the k-mer starting there anywhere, on either strand --
+        one label per assembly, 0 .. ``n_groups - 1`` or 255 to leave the assembly out, ``n_groups`` (1..8) as the pileup takes it:
+        the result then answers ``profile()``, a :class:`KmerProfile`.  ``copies=True`` (it needs ``profile``, else ValueError) also
+        counts the copies every group holds.  With ``kmerlen`` an oligo's length this is the exact-match inclusivity and exclusivity
+        of every window at once; it proposes, :meth:`oligo_hits` confirms.  No mismatches, no Tm, no dG."""
+        if copies and profile is None:
+            raise ValueError("copies=True needs profile=groups: the copies are counted per group")
         qs = [q.encode("utf-8") if isinstance(q, str) else bytes(q) for q in queries]
         offs = np.zeros(len(qs) + 1, np.uint64)
         np.cumsum([len(q) for q in qs], out=offs[1:])
         h = c_vp()
-        check(lib.sw_batch_screen(self._h, _ptr(offs), b"".join(qs), c_u64(len(qs)), c_u64(int(kmerlen)), c_vp(stream), ctypes.byref(h)))
-        return Screen(h)
+        if profile is None:
+            check(lib.sw_batch_screen(self._h, _ptr(offs), b"".join(qs), c_u64(len(qs)), c_u64(int(kmerlen)), c_vp(stream), ctypes.byref(h)))
+            return Screen(h)
+        lab, ng = _pile_groups(profile, self.info()["n_assemblies"], n_groups, "assembly")
+        check(lib.sw_batch_screen_profile(self._h, _ptr(offs), b"".join(qs), c_u64(len(qs)), c_u64(int(kmerlen)), _ptr(lab), c_u64(ng),
+                                          ctypes.c_int(1 if copies else 0), c_vp(stream), ctypes.byref(h)))
+        return Screen(h, offsets=offs, copies=bool(copies))
 
     def infix_distances(self, queries, pairs, stats: bool = False):
         """``(dist, end)`` of the infix edit distance of queries against intervals of the batch (csrc/hits.hip, DESIGN.md section
@@ -832,13 +845,14 @@ class Markers:
         check(lib.sw_markers_row_distances(self._h, batch._h, _ptr(sel), c_u64(len(sel)), _ptr(dist), _ptr(strand), c, ms))
         return (dist, strand, _distance_stats(c, ms)) if stats else (dist, strand)
 
-    def screen(self, batch: "Batch", kmerlen: int, select=None) -> "Screen":
+    def screen(self, batch: "Batch", kmerlen: int, select=None, profile=None, n_groups=None, copies: bool = False) -> "Screen":
         """:meth:`Batch.screen` of the representatives' text -- ``sequences(batch, "reps", select)``, in that order -- against every
         assembly of ``batch``.  A flagged (inexact) representative is screened as fetched: its ``N``s carry no k-mers.  ``kmerlen``
-        is the caller's choice; it need not be the graph's k."""
+        is the caller's choice; it need not be the graph's k.  ``profile``, ``n_groups`` and ``copies`` are that call's: the k-mer
+        profile of every position of every representative, by group of assembly."""
         offs, blob, _ = self.sequences(batch, "reps", select)
         o = offs.astype(np.int64)
-        return batch.screen([blob[o[i]:o[i + 1]] for i in range(len(o) - 1)], kmerlen)
+        return batch.screen([blob[o[i]:o[i + 1]] for i in range(len(o) - 1)], kmerlen, profile=profile, n_groups=n_groups, copies=copies)
 
     def best_hits(self, batch: "Batch", kmerlen: int, select=None, align: bool = False, loci: bool = False, min_seeds: int = 1,
                   seed_copies=None, local: bool = False, scoring=(2, -3, 5, 2), pileup=None, n_groups=None, max_dist_permille: int = 1000,
@@ -1008,10 +1022,19 @@ class Screen:
     """Exact k-mer containment counts of a list of queries in every assembly of a batch, resident on the device
     (:meth:`Batch.screen`, :meth:`Markers.screen`; csrc/screen.hip).  It stands where ``eval_markers`` (src/seqwin/markers.py:607-696)
     BLASTs the representatives, has no counterpart in the reference, is not BLAST and fills none of ``MarkerMetrics``.
-    ``rows`` (queries) / ``cols`` (assemblies) are None (all), a ``(lo, hi)`` pair, a slice or a range."""
+    ``rows`` (queries) / ``cols`` (assemblies) are None (all), a ``(lo, hi)`` pair, a slice or a range.  A screen made with
+    ``profile=groups`` also answers :meth:`profile`."""
 
-    def __init__(self, handle: c_vp):
+    def __init__(self, handle: c_vp, offsets=None, copies: bool = False):
         self._h = handle
+        self._offs = None if offsets is None else np.array(offsets, np.uint64)   # (of a call with a profile)
+        self._copies = bool(copies)
+
+    def profile(self) -> "KmerProfile":
+        """The :class:`KmerProfile` of a screen made with ``profile=groups``; ValueError for any other."""
+        if self._offs is None:
+            raise ValueError("this screen was made without a profile (screen(..., profile=groups) makes one)")
+        return KmerProfile(self, self._offs, self._copies)
 
     def sizes(self):
         """(queries, assemblies, distinct canonical k-mers of all queries, k)"""
@@ -1063,6 +1086,79 @@ class Screen:
             self.close()
         except Exception:
             pass
+
+
+class KmerProfile:
+    """Per position of every query and per group of assemblies: in how many assemblies of the group the canonical k-mer of the window
+    that starts there occurs anywhere (``present``), and how many valid windows of those assemblies hold it (``copies``, with
+    ``copies=True``) -- ``Screen.profile()`` of a ``screen(..., profile=groups)``; csrc/screen.hip, DESIGN.md section 3.2m.  Every locus
+    of every assembly on both strands, exactly; a window counts once whatever its strand.  A row where no window starts (the last
+    k - 1 bytes of a query, a window with an invalid byte, a query shorter than k) reads ``NO_WINDOW`` in ``present`` and
+    ``NO_WINDOW_COPIES`` in ``copies``.  It has no counterpart in the reference, is not BLAST and fills none of ``MarkerMetrics``:
+    no mismatches, no Tm, no dG.  :mod:`seqwin_amd.kprofile` reads it."""
+
+    NO_WINDOW = 0xFFFFFFFF
+    NO_WINDOW_COPIES = 0xFFFFFFFFFFFFFFFF
+
+    def __init__(self, screen: "Screen", offsets: np.ndarray, copies: bool):
+        self._screen = screen   # (the tables live in the screen's handle)
+        self._offs = np.array(offsets, np.uint64)
+        self._has_copies = bool(copies)
+        self._tab = None
+
+    @property
+    def k(self) -> int:
+        return self._screen.sizes()[3]
+
+    def sizes(self):
+        """(rows: the bytes of all queries, groups, whether copies were counted)"""
+        v = [c_u64() for _ in range(3)]
+        check(lib.sw_screen_profile_sizes(self._screen._h, *[ctypes.byref(x) for x in v]))
+        return v[0].value, v[1].value, bool(v[2].value)
+
+    def _export(self):
+        if self._tab is None:
+            rows, ng, has = self.sizes()
+            present = np.empty((rows, ng), np.uint32)
+            cop = np.empty((rows, ng), np.uint64) if has else None
+            sizes = np.empty(ng, np.uint32)
+            check(lib.sw_screen_profile_export(self._screen._h, _ptr(present), _ptr(cop) if has else None, _ptr(sizes)))
+            self._tab = (present, cop, sizes)
+        return self._tab
+
+    def _query(self, q: int):
+        q = int(q)
+        if not 0 <= q < len(self._offs) - 1:
+            raise ValueError(f"query {q} is none of the call's {len(self._offs) - 1}")
+        return int(self._offs[q]), int(self._offs[q + 1])
+
+    def present(self, q: int) -> np.ndarray:
+        """uint32[len(query q), groups]"""
+        lo, hi = self._query(q)
+        return self._export()[0][lo:hi].copy()
+
+    def copies(self, q: int) -> np.ndarray:
+        """uint64[len(query q), groups]; ValueError for a profile made without ``copies=True``."""
+        if not self._has_copies:
+            raise ValueError("this profile was made without copies (screen(..., profile=groups, copies=True) counts them)")
+        lo, hi = self._query(q)
+        return self._export()[1][lo:hi].copy()
+
+    def table(self):
+        """``(offsets, present uint32[total, groups], copies uint64[total, groups] or None)``: the rows of query q are
+        ``[offsets[q], offsets[q + 1])``."""
+        present, cop, _ = self._export()
+        return self._offs.copy(), present.copy(), None if cop is None else cop.copy()
+
+    def group_sizes(self) -> np.ndarray:
+        """uint32[groups]: the assemblies of every label."""
+        return self._export()[2].copy()
+
+    def stats(self) -> dict:
+        c = (c_u64 * 2)()
+        ms = (ctypes.c_double * 2)()
+        check(lib.sw_screen_profile_stats(self._screen._h, c, ms))
+        return dict(table_bytes=int(c[0]), copy_adds=int(c[1]), profile_ms=ms[0], gather_ms=ms[1])
 
 
 SITE_FIELDS = ("oligo", "assembly", "record", "pos", "strand", "mm")
