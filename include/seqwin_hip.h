@@ -769,6 +769,30 @@ int sw_oligos_sites(const sw_oligos *h, uint64_t *cell_offsets, uint32_t *oligo,
  * the site buffer, chunks redone in halves, window x pattern comparisons (a pattern = an oligo on a strand) }; ms[2] = { scan, order
  * of the site list } (HIP events). */
 int sw_oligos_stats(const sw_oligos *h, uint64_t *counters, double *ms);
+/* ---- oligo search with indels (csrc/oligo.hip; tests/tools/oligo_edit_host.py restates it) ----
+ * The same object by unit-cost edit distance.  On a valid run T of n bases and strand 0, with Q the oligo without its last
+ * three_prime = c letters: E(e) = the least ed(Q, T[b : e - c]) over b if the c bases before the end e face the clamp's sets, else
+ * infinite; D(e) = min(E(e), d + 1).  The end e is a site iff D(e) <= d, D > D(e) on the d ends before it and D >= D(e) on the d ends
+ * after it, inside the run.  Its alignment is the canonical traceback of section 3.2f (rules =, X, I, D in that order) from
+ * (|Q|, e - c) until the oligo is used up: pos where it stops, mismatch = #X, gaps = #I + #D, dist = mismatch + gaps = D(e).  Strand 1 is
+ * strand 0 on the run's reverse complement, the interval mapped back.  Per cell the best site is the least in (dist, record, pos,
+ * strand), then end.  The list is ordered by (oligo, assembly, record, pos, end, strand). */
+/* (no counterpart in the reference)  As sw_batch_oligo_hits.  max_edits in 0..4, three_prime in 0..8, max_edits + three_prime below
+ * the shortest oligo: anything else -> SW_ERR_VALUE before a device is touched.  max_edits = 0 gives the sites of max_mismatch = 0. */
+int sw_batch_oligo_hits_edit(const sw_batch *batch, const uint64_t *offsets, const char *blob, uint64_t n_oligos, uint64_t max_edits,
+                             uint64_t three_prime, int want_sites, void *stream, sw_oligos **out);
+/* (no counterpart in the reference)  max_edits of the call; -1 for a result of sw_batch_oligo_hits.  On a result with max_edits
+ * sw_oligos_block's field 1 and sw_oligos_sites' mm hold dist, and sw_oligos_block has the fields 5 best_end, 6 best_mismatch and
+ * 7 best_gaps; on a Hamming result these three answer pos + L, mm and 0. */
+int sw_oligos_max_edits(const sw_oligos *h, int64_t *max_edits);
+/* (no counterpart in the reference)  sw_oligos_sites with the columns end, mismatch and gaps in place of mm (dist is their sum); a
+ * Hamming result answers pos + L, mm and 0. */
+int sw_oligos_sites_edit(const sw_oligos *h, uint64_t *cell_offsets, uint32_t *oligo, uint32_t *assembly, uint32_t *record, uint32_t *pos,
+                         uint32_t *strand, uint32_t *end, uint32_t *mismatch, uint32_t *gaps);
+/* (no counterpart in the reference)  counters[2] = { steps of the bit-vector column (an upper bound: every lane with an end counts
+ * L + 3 max_edits - 1 steps more than it has ends, per oligo and strand), candidates resolved }; ms[1] = { the resolve kernel };
+ * zeros for a Hamming result.  With max_edits sw_oligos_stats' scan time excludes the resolve kernel. */
+int sw_oligos_edit_stats(const sw_oligos *h, uint64_t *counters, double *ms);
 /* (no counterpart in the reference) */
 void sw_oligos_free(sw_oligos *h);
 

@@ -21,7 +21,19 @@
 //   k_ol_decode    a sorted site key -> assembly, record, pos
 // Oligos are taken in groups (a pass over the batch each), assemblies in chunks bounded by the site buffer: a chunk that overflows
 // is redone in two halves, one assembly that overflows has the buffer doubled -- as hits.hip treats its key buffer.
+//
+// With max_edits the same object is made by a second route (tests/tools/oligo_edit_host.py): unit-cost edit
+// distance in place of the mismatch count, so that a site with a one-base bulge is found.  oligo_edit_core.hpp holds its arithmetic.
+//   k_ole_scan     the tiles cover the runs of Lmin - d bases or more.  A lane owns the same 16 places of a tile twice: as ends on
+//                  strand 0 and as starts -- the ends of the reverse complement -- on strand 1.  Per strand it keeps up to 59 bases
+//                  around them as two 64-bit planes, in reading order; per oligo (a uniform loop, the Eq row by scalar loads) it steps
+//                  Myers' column over them and applies the local-minimum rule in registers.  A candidate is appended as
+//                  (oligo, strand, a base of the run that names the end).
+//   k_ole_resolve  a thread per candidate: the small matrix and the canonical traceback give pos, end, mismatch and gaps; the site is
+//                  counted, offered as the cell's best (64-bit atomicMin) and its buffer entry becomes the sortable site key
+//   k_ole_best     the best site's key -> the seven best fields of a cell;  k_ole_decode  a sorted site key -> assembly, record, pos
 #include "screen_core.hpp"
+#include "oligo_edit_core.hpp"
 
 namespace sw {
 namespace {
@@ -188,6 +200,129 @@ __global__ __launch_bounds__(SCR_TPB) void k_ol_decode(uint64_t base, uint64_t e
     pos[i] = v.run_pos[r] + (uint32_t)(idx - v.run_base[r]);
 }
 
+// ---- the route with indels (section 3.2n) ---------------------------------------------------------------------------------------------
+constexpr uint32_t OLE_MAX_EDITS = ole::MAX_EDITS;
+constexpr uint64_t OLE_IDX_MASK = (1ull << 43) - 1;
+// candidate: oligo of the pass << 44 | strand << 43 | a base of the run (strand 0: the end's last base, strand 1: the site's first)
+constexpr uint32_t OLE_CAND_Q_SHIFT = 44, OLE_CAND_STRAND_SHIFT = 43;
+// site key: oligo << 52 | index of pos << 9 | (end - pos - (L - d)) << 5 | strand << 4 | code;  code = 5 t + mismatch, gaps = |end - pos - L| + 2 t
+// best key: dist << 61 | index of pos << 9 | strand << 8 | (end - pos - (L - d)) << 4 | code
+constexpr uint32_t OLE_SITE_Q_SHIFT = 52, OLE_IDX_SHIFT = 9, OLE_BEST_DIST_SHIFT = 61;
+
+struct EditScanArgs {
+    RunView v;                       // the tiles of this launch (runs of k = lmin - d bases or more)
+    const uint32_t *tab;             // [n_q][ole::ROW] the pass's oligos
+    uint32_t n_q, k, d, c;
+    unsigned long long *buf;         // candidates of the chunk
+    unsigned long long cap;
+    unsigned long long *cursor;      // candidates appended (above cap: the chunk overflowed, it is redone)
+};
+
+__global__ __launch_bounds__(KW_TPB) void k_ole_scan(EditScanArgs g)
+{
+    const uint32_t lane = threadIdx.x % KW_WAVE;
+    uint32_t r, n_mine;
+    uint64_t first;
+    if (!wave_tile(g.v, lane, r, first, n_mine)) return;   // (the whole wave)
+    if (*(volatile unsigned long long *)g.cursor > g.cap) return;   // (the whole wave: the chunk has overflowed, it is redone anyway)
+    const uint64_t run_base = g.v.run_base[r];
+    const uint32_t n = g.v.run_nk[r] + g.k - 1;           // bases of the run
+    ole::OleStream S[2] = {};
+    uint32_t a[2] = {0, 0};
+    if (n_mine) {
+#pragma unroll
+        for (uint32_t s = 0; s < 2; ++s) {
+            a[s] = ole::first_end(s, n, g.k, (uint32_t)first, n_mine);
+            S[s] = ole::load_stream(g.v.packed, run_base, n, s, a[s], n_mine, g.d);
+        }
+    }
+    const ol_table_t tab = (ol_table_t)g.tab;
+    for (uint32_t q = 0; q < g.n_q; ++q) {      // (uniform)
+        const ol_table_t row = tab + (uint64_t)q * ole::ROW;
+        const uint32_t e0 = row[0], e1 = row[1], e2 = row[2], e3 = row[3], len = row[4];
+#pragma unroll
+        for (uint32_t s = 0; s < 2; ++s) {
+            const uint32_t cand = n_mine ? ole::ole_scan(S[s], a[s], n_mine, n, g.d, g.c, len, e0, e1, e2, e3) : 0u;
+            if (!__ballot(cand != 0)) continue;     // (uniform) candidates are rare
+            const WaveRange w = wave_append(g.cursor, lane, (uint32_t)__popc(cand));
+            if (!w.total || w.base + w.total > g.cap) continue;   // (uniform) overflow: the host reads it from the cursor
+            uint32_t at = 0;
+            for (uint32_t x = 0; x < KW_L; ++x) {
+                if (!((cand >> x) & 1)) continue;
+                const uint32_t e = a[s] + x;        // (1..n)
+                const unsigned long long anchor = run_base + (s ? n - e : e - 1);
+                g.buf[w.base + w.offset + at] = ((unsigned long long)q << OLE_CAND_Q_SHIFT) | ((unsigned long long)s << OLE_CAND_STRAND_SHIFT) | anchor;
+                ++at;
+            }
+        }
+    }
+}
+
+// candidate i of the chunk: its alignment; the site is counted, offered as its cell's best, and buf[i] becomes its site key
+__global__ __launch_bounds__(SCR_TPB) void k_ole_resolve(uint64_t base, uint64_t end, unsigned long long *__restrict__ buf, const uint32_t *__restrict__ tab,
+                                                         uint32_t q0, RunView v, uint32_t k, uint32_t d, uint32_t c, uint64_t n_asm,
+                                                         uint32_t *__restrict__ n_sites, unsigned long long *__restrict__ best)
+{
+    const uint64_t i = base + (uint64_t)blockIdx.x * SCR_TPB + threadIdx.x;
+    if (i >= end) return;
+    const unsigned long long raw = buf[i];
+    const uint32_t ql = (uint32_t)(raw >> OLE_CAND_Q_SHIFT), s = (uint32_t)(raw >> OLE_CAND_STRAND_SHIFT) & 1u;
+    const uint64_t anchor = raw & OLE_IDX_MASK;
+    const uint32_t r = ol_run_of(v.run_base, v.n_runs, anchor);
+    const uint64_t run_base = v.run_base[r];
+    const uint32_t n = v.run_nk[r] + k - 1, off = (uint32_t)(anchor - run_base);
+    const uint32_t e = s ? n - off : off + 1;
+    const uint32_t *row = tab + (uint64_t)ql * ole::ROW;
+    const uint32_t eq[4] = {row[0], row[1], row[2], row[3]}, len = row[4];
+    const ole::OleSite site = ole::ole_align(v.packed, run_base, n, s, e, d, c, len, eq);
+    const uint32_t pos = s ? n - e : site.b, stop = s ? n - site.b : e;
+    const uint32_t over = (stop - pos - (len - d)) & 15u;                    // (0..2 d)
+    const uint32_t skew = over > d ? over - d : d - over;                    // |#D - #I|
+    const uint32_t code = 5 * ((site.gaps - skew) >> 1) + site.mismatch;     // (gaps = skew + 2 t, t <= 2, mismatch <= 4)
+    const unsigned long long idx = run_base + pos, low = ((unsigned long long)over << 4) | code;
+    const uint64_t a = v.run_asm[r];
+    atomicAdd(n_sites + (uint64_t)(q0 + ql) * n_asm + a, 1u);
+    atomicMin(best + (uint64_t)ql * n_asm + a, ((unsigned long long)site.dist << OLE_BEST_DIST_SHIFT) | (idx << OLE_IDX_SHIFT) | ((unsigned long long)s << 8) | low);
+    buf[i] = ((unsigned long long)(q0 + ql) << OLE_SITE_Q_SHIFT) | (idx << OLE_IDX_SHIFT) | ((unsigned long long)over << 5) | ((unsigned long long)s << 4) | code;
+}
+
+struct BestFields {
+    uint32_t *dist, *rec, *pos, *strand, *end, *mismatch, *gaps;
+};
+
+// cell i of the pass with a site: the seven fields of its best one
+__global__ __launch_bounds__(SCR_TPB) void k_ole_best(uint64_t base, uint64_t end, const unsigned long long *__restrict__ best, uint64_t cell0, RunView v,
+                                                      const uint32_t *__restrict__ tab, uint64_t n_asm, uint32_t d, BestFields f)
+{
+    const uint64_t i = base + (uint64_t)blockIdx.x * SCR_TPB + threadIdx.x;
+    if (i >= end) return;
+    const unsigned long long key = best[i];
+    if (key == OL_NONE) return;   // (the fields hold 0xFFFFFFFF)
+    const uint64_t idx = (key >> OLE_IDX_SHIFT) & OLE_IDX_MASK;
+    const uint32_t r = ol_run_of(v.run_base, v.n_runs, idx);
+    const uint32_t len = tab[(i / n_asm) * ole::ROW + 4], over = (uint32_t)(key >> 4) & 15u, code = (uint32_t)key & 15u;
+    const uint32_t pos = v.run_pos[r] + (uint32_t)(idx - v.run_base[r]);
+    f.dist[cell0 + i] = (uint32_t)(key >> OLE_BEST_DIST_SHIFT);
+    f.rec[cell0 + i] = v.run_rec[r];
+    f.pos[cell0 + i] = pos;
+    f.strand[cell0 + i] = (uint32_t)(key >> 8) & 1u;
+    f.end[cell0 + i] = pos + len - d + over;
+    f.mismatch[cell0 + i] = code % 5;
+    f.gaps[cell0 + i] = (over > d ? over - d : d - over) + 2 * (code / 5);
+}
+
+__global__ __launch_bounds__(SCR_TPB) void k_ole_decode(uint64_t base, uint64_t end, const uint64_t *__restrict__ keys, RunView v, uint32_t *__restrict__ asm_out,
+                                                        uint32_t *__restrict__ rec, uint32_t *__restrict__ pos)
+{
+    const uint64_t i = base + (uint64_t)blockIdx.x * SCR_TPB + threadIdx.x;
+    if (i >= end) return;
+    const uint64_t idx = (keys[i] >> OLE_IDX_SHIFT) & OLE_IDX_MASK;
+    const uint32_t r = ol_run_of(v.run_base, v.n_runs, idx);
+    asm_out[i] = v.run_asm[r];
+    rec[i] = v.run_rec[r];
+    pos[i] = v.run_pos[r] + (uint32_t)(idx - v.run_base[r]);
+}
+
 // ---- host: the oligos -------------------------------------------------------------------------------------------------------------
 // the set of bases a letter stands for (bit b: base b of A C G T), 0: no letter of an oligo
 uint32_t iupac_set(unsigned char c)
@@ -266,13 +401,18 @@ void pattern_rows(const char *text, uint32_t len, uint32_t clamp, uint32_t *rows
 struct sw_oligos {
     int device = 0;
     uint64_t nq = 0, n_asm = 0, max_mm = 0, three_prime = 0;
-    sw::DevArray<uint32_t> field[5];       // [nq][n_asm] n_sites, best_mm, best_record, best_pos, best_strand
+    int64_t max_edits = -1;                // -1: a Hamming result
+    std::vector<uint32_t> lens;            // [nq] the oligos' lengths
+    sw::DevArray<uint32_t> field[8];       // [nq][n_asm] n_sites, best_mm (an edit result: best_dist), best_record, best_pos, best_strand;
+                                           // an edit result only: best_end, best_mismatch, best_gaps
     bool has_sites = false;
     uint64_t n_list = 0;
     sw::DevArray<uint64_t> keys;           // [n_list] the site keys, ascending
     sw::DevArray<uint32_t> s_asm, s_rec, s_pos;
     uint64_t counters[8] = {};             // sw_oligos_stats
     double ms[2] = {};                     // scan, order
+    uint64_t edit_counters[2] = {};        // sw_oligos_edit_stats: DP steps, candidates resolved
+    double resolve_ms = 0;
 };
 
 namespace sw {
@@ -290,6 +430,7 @@ void batch_oligo_hits(const sw_batch &b, const uint64_t *offsets, const char *bl
     o.max_mm = max_mm;
     o.three_prime = three_prime;
     o.has_sites = want_sites;
+    for (uint64_t q = 0; q < nq; ++q) o.lens.push_back((uint32_t)(offsets[q + 1] - offsets[q]));
     for (int f = 0; f < 5; ++f) {
         o.field[f].alloc(cells);
         if (cells) SW_HIP(hipMemsetAsync(o.field[f].p, f ? 0xFF : 0, cells * 4, stream));
@@ -401,6 +542,172 @@ void batch_oligo_hits(const sw_batch &b, const uint64_t *offsets, const char *bl
     memcpy(o.counters, cn, sizeof cn);
 }
 
+// ---- the route with indels ---------------------------------------------------------------------------------------------------------
+// what max_edits adds to check_oligos
+void check_edits(uint32_t lmin, uint64_t max_edits, uint64_t three_prime)
+{
+    if (max_edits > OLE_MAX_EDITS) raise(SW_ERR_VALUE, "oligo hits: max_edits must lie in 0..%u (got %llu)", OLE_MAX_EDITS, (unsigned long long)max_edits);
+    if (max_edits + three_prime >= lmin)
+        raise(SW_ERR_VALUE, "oligo hits: max_edits + three_prime must lie below the shortest oligo's %u letters (got %llu + %llu)", lmin,
+              (unsigned long long)max_edits, (unsigned long long)three_prime);
+}
+
+// the row of oligo `text`: bit i of plane b is set iff base b lies in the set of position i; the length
+void edit_row(const char *text, uint32_t len, uint32_t *row)
+{
+    memset(row, 0, ole::ROW * sizeof(uint32_t));
+    for (uint32_t i = 0; i < len; ++i) {
+        const uint32_t s = iupac_set((unsigned char)text[i]);
+        for (uint32_t b = 0; b < 4; ++b)
+            if ((s >> b) & 1) row[b] |= 1u << i;
+    }
+    row[4] = len;
+}
+
+// As batch_oligo_hits: groups of oligos, chunks of assemblies bounded by the buffer, halves and doublings on overflow, one sort.  The
+// buffer holds the chunk's candidates whether or not the list is wanted: k_ole_resolve reads them.  Nothing is counted before a chunk
+// is known to fit, so a chunk that is redone leaves nothing behind.
+void batch_oligo_edit(const sw_batch &b, const uint64_t *offsets, const char *blob, uint64_t nq, uint32_t lmin, uint32_t d, uint32_t three_prime,
+                      bool want_sites, hipStream_t stream, sw_oligos &o)
+{
+    const HostBatch &h = b.host;
+    const uint64_t n_asm = h.n_assemblies, cells = nq * n_asm;
+    if (h.rec_len.size() && !b.d_packed.p) raise(SW_ERR_VALUE, "oligo hits: the batch holds no packed bases (it must be resident)");
+    if ((uint64_t)h.packed_words32() * 16 >= OL_MAX_BASES) raise(SW_ERR_RUNTIME, "oligo hits: the batch has 2^43 bases or more");
+    o.nq = nq;
+    o.n_asm = n_asm;
+    o.max_mm = 0;
+    o.max_edits = d;
+    o.three_prime = three_prime;
+    o.has_sites = want_sites;
+    for (uint64_t q = 0; q < nq; ++q) o.lens.push_back((uint32_t)(offsets[q + 1] - offsets[q]));
+    for (int f = 0; f < 8; ++f) {
+        o.field[f].alloc(cells);
+        if (cells) SW_HIP(hipMemsetAsync(o.field[f].p, f ? 0xFF : 0, cells * 4, stream));
+    }
+    const uint32_t k = lmin - d;   // a site spans L - d bases or more
+    RunTiles T;
+    build_run_tiles(h, k, "oligo hits", T);
+    std::vector<uint64_t> asm_lanes(n_asm + 1, 0);   // lanes with an end, of the assemblies before a
+    for (uint64_t r = 0; r < T.n_runs; ++r) asm_lanes[T.run_asm[r] + 1] += (T.run_nk[r] + KW_L - 1) / KW_L;
+    for (uint64_t a = 0; a < n_asm; ++a) asm_lanes[a + 1] += asm_lanes[a];
+    uint64_t group = OL_GROUP, budget = OL_BUFFER_BYTES;
+    if (const char *e = SW_TEST_GETENV("SEQWIN_AMD_OLIGO_GROUP")) group = std::min<uint64_t>(std::max<uint64_t>(env_u64(e, group), 1), OL_GROUP);
+    if (const char *e = SW_TEST_GETENV("SEQWIN_AMD_OLIGO_BUFFER_KB")) budget = env_u64(e, budget >> 10) << 10;
+    group = std::min<uint64_t>(group, nq);
+    uint64_t cap = std::min<uint64_t>(std::max<uint64_t>(budget / 8, 1), OL_MAX_SITES);
+    const uint32_t blocks_max = launch_blocks("SEQWIN_AMD_OLIGO_MAX_BLOCKS");
+    uint64_t passes = 0, chunks = 0, launches = 0, hits = 0, grows = 0, splits = 0, windows = 0, comparisons = 0, steps = 0;
+    double resolve_ms = 0;
+    std::vector<DevArray<uint64_t>> lists;
+    Event e0, e1, e2, ra, rb;
+    SW_HIP(hipEventRecord(e0, stream));
+    DevRunTiles runs(T, b.d_packed.p, stream, true);
+    if (T.tiles && cells) {
+        std::vector<uint32_t> rows_host(group * ole::ROW);
+        DevArray<uint32_t> tab(group * ole::ROW);
+        DevArray<unsigned long long> best(group * n_asm), d_cursor(1), buf(cap);
+        EditScanArgs g{};
+        g.tab = tab.p;
+        g.k = k;
+        g.d = d;
+        g.c = three_prime;
+        g.cursor = d_cursor.p;
+        const BestFields bf{o.field[1].p, o.field[2].p, o.field[3].p, o.field[4].p, o.field[5].p, o.field[6].p, o.field[7].p};
+        uint64_t rows = n_asm;
+        for (uint64_t q0 = 0; q0 < nq; q0 += group, ++passes) {
+            const uint64_t qn = std::min<uint64_t>(group, nq - q0);
+            uint64_t len_sum = 0;
+            for (uint64_t q = 0; q < qn; ++q) {
+                edit_row(blob + offsets[q0 + q], o.lens[q0 + q], rows_host.data() + q * ole::ROW);
+                len_sum += o.lens[q0 + q];
+            }
+            SW_HIP(hipMemcpyAsync(tab.p, rows_host.data(), qn * ole::ROW * 4, hipMemcpyHostToDevice, stream));
+            SW_HIP(hipMemsetAsync(best.p, 0xFF, qn * n_asm * 8, stream));
+            g.n_q = (uint32_t)qn;
+            for (uint64_t a0 = 0; a0 < n_asm;) {
+                const uint64_t a1 = std::min<uint64_t>(n_asm, a0 + rows);
+                SW_HIP(hipMemsetAsync(d_cursor.p, 0, 8, stream));
+                g.buf = buf.p;
+                g.cap = cap;
+                g.v = runs.view(T.asm_tile_off[a0], T.asm_tile_off[a1]);
+                launches += launch_tiles(k_ole_scan, g, blocks_max, stream);
+                unsigned long long n = 0;
+                SW_HIP(hipMemcpyAsync(&n, d_cursor.p, 8, hipMemcpyDeviceToHost, stream));
+                SW_HIP(hipStreamSynchronize(stream));   // (the rows of the host are free again, too)
+                if (n > cap) {
+                    if (a1 - a0 > 1) {   // redone in two halves: the first now, the second is the next chunk
+                        rows = (a1 - a0 + 1) / 2;
+                        ++splits;
+                    } else {             // one assembly above the budget: the buffer doubles
+                        if (cap >= OL_MAX_SITES) raise(SW_ERR_RUNTIME, "oligo hits: assembly %llu alone has 2^32 sites or more", (unsigned long long)a0);
+                        cap = std::min<uint64_t>(cap * 2, OL_MAX_SITES);
+                        buf.alloc(cap);
+                        ++grows;
+                    }
+                    continue;
+                }
+                const uint64_t ends = T.asm_kmers[a1] - T.asm_kmers[a0], lanes = asm_lanes[a1] - asm_lanes[a0];
+                hits += n;
+                windows += ends;
+                comparisons += ends * 2 * qn;
+                steps += 2 * (qn * ends + lanes * (len_sum + qn * 3 * d - qn));   // a lane steps L + 3 d - 1 bases more than it has ends
+                ++chunks;
+                if (n) {
+                    if (want_sites && hits >= OL_MAX_SITES) raise(SW_ERR_RUNTIME, "oligo hits: a site list of 2^32 entries or more");
+                    SW_HIP(hipEventRecord(ra, stream));
+                    launch_1d(k_ole_resolve, n, stream, buf.p, (const uint32_t *)tab.p, (uint32_t)q0, runs.view(), k, d, three_prime, n_asm, o.field[0].p, best.p);
+                    SW_HIP(hipEventRecord(rb, stream));
+                    if (want_sites) {
+                        lists.emplace_back((size_t)n);
+                        SW_HIP(hipMemcpyAsync(lists.back().p, buf.p, n * 8, hipMemcpyDeviceToDevice, stream));
+                    }
+                    SW_HIP(hipEventSynchronize(rb));
+                    float ms = 0;
+                    SW_HIP(hipEventElapsedTime(&ms, ra, rb));
+                    resolve_ms += ms;
+                }
+                a0 = a1;
+            }
+            launch_1d(k_ole_best, qn * n_asm, stream, (const unsigned long long *)best.p, q0 * n_asm, runs.view(), (const uint32_t *)tab.p, n_asm, d, bf);
+            SW_HIP(hipStreamSynchronize(stream));   // (the table and the rows are rewritten by the next pass)
+        }
+    }
+    SW_HIP(hipEventRecord(e1, stream));
+    // ---- the site list: all chunks' keys in one ascending order = (oligo, assembly, record, pos, end, strand) ----
+    if (want_sites && hits) {
+        DevArray<uint64_t> ka(hits), kb(hits);
+        uint64_t at = 0;
+        for (DevArray<uint64_t> &l : lists) {
+            SW_HIP(hipMemcpyAsync(ka.p + at, l.p, l.n * 8, hipMemcpyDeviceToDevice, stream));
+            at += l.n;
+        }
+        if (at != hits) raise(SW_ERR_RUNTIME, "internal error: the chunks' site lists do not add up");
+        uint64_t *kp = ka.p, *ap = kb.p;
+        sort_all_bits(kp, ap, hits, stream);
+        lists.clear();
+        if (kp != ka.p) std::swap(ka, kb);
+        o.keys = std::move(ka);
+        o.n_list = hits;
+        o.s_asm.alloc(hits);
+        o.s_rec.alloc(hits);
+        o.s_pos.alloc(hits);
+        launch_1d(k_ole_decode, hits, stream, (const uint64_t *)o.keys.p, runs.view(), o.s_asm.p, o.s_rec.p, o.s_pos.p);
+    }
+    SW_HIP(hipEventRecord(e2, stream));
+    SW_HIP(hipStreamSynchronize(stream));   // (the temporaries go back to the pool behind the kernels)
+    float ms = 0;
+    SW_HIP(hipEventElapsedTime(&ms, e0, e1));
+    o.ms[0] = std::max(0.0, (double)ms - resolve_ms);
+    SW_HIP(hipEventElapsedTime(&ms, e1, e2));
+    o.ms[1] = ms;
+    o.resolve_ms = resolve_ms;
+    const uint64_t cn[8] = {windows, passes, chunks, launches, hits, grows, splits, comparisons};
+    memcpy(o.counters, cn, sizeof cn);
+    o.edit_counters[0] = steps;
+    o.edit_counters[1] = hits;
+}
+
 }  // namespace
 }  // namespace sw
 
@@ -438,7 +745,9 @@ int sw_oligos_block(const sw_oligos *h, uint64_t field, uint64_t r0, uint64_t r1
 {
     return guarded([&] {
         if (!h) raise(SW_ERR_VALUE, "oligo hits: a NULL handle");
-        if (field > 4) raise(SW_ERR_VALUE, "oligo hits: field %llu; 0 n_sites, 1 best_mm, 2 best_record, 3 best_pos, 4 best_strand", (unsigned long long)field);
+        if (field > 7)
+            raise(SW_ERR_VALUE, "oligo hits: field %llu; 0 n_sites, 1 best_mm, 2 best_record, 3 best_pos, 4 best_strand, 5 best_end, 6 best_mismatch, 7 best_gaps",
+                  (unsigned long long)field);
         if (r0 > r1 || r1 > h->nq || c0 > c1 || c1 > h->n_asm)
             raise(SW_ERR_VALUE, "oligo hits: rows [%llu, %llu) x columns [%llu, %llu) lie outside the %llu oligos x %llu assemblies", (unsigned long long)r0,
                   (unsigned long long)r1, (unsigned long long)c0, (unsigned long long)c1, (unsigned long long)h->nq, (unsigned long long)h->n_asm);
@@ -446,7 +755,14 @@ int sw_oligos_block(const sw_oligos *h, uint64_t field, uint64_t r0, uint64_t r1
         if (!nr || !nc) return;
         if (!out) raise(SW_ERR_VALUE, "oligo hits: a NULL handle or array");
         require_device(h->device, "the oligo hits");
-        SW_HIP(hipMemcpy2D(out, nc * 4, h->field[field].p + r0 * h->n_asm + c0, h->n_asm * 4, nc * 4, nr, hipMemcpyDeviceToHost));
+        // a Hamming result keeps no end, mismatch or gaps: they follow from pos + L, mm and 0
+        const bool derived = field > 4 && h->max_edits < 0;
+        const uint64_t src = !derived ? field : field == 5 ? 3 : 1;
+        SW_HIP(hipMemcpy2D(out, nc * 4, h->field[src].p + r0 * h->n_asm + c0, h->n_asm * 4, nc * 4, nr, hipMemcpyDeviceToHost));
+        if (derived && field != 6)
+            for (uint64_t r = 0; r < nr; ++r)
+                for (uint64_t c = 0; c < nc; ++c)
+                    if (out[r * nc + c] != 0xFFFFFFFFu) out[r * nc + c] = field == 5 ? out[r * nc + c] + h->lens[r0 + r] : 0;
     });
 }
 
@@ -459,31 +775,97 @@ int sw_oligos_sites_size(const sw_oligos *h, uint64_t *n_sites_total)
     });
 }
 
+// the list's columns of either kind of result; dist (a Hamming result: mm), end, mismatch and gaps may each be NULL
+static void site_columns(const sw_oligos *h, uint64_t *cell_offsets, uint32_t *oligo, uint32_t *assembly, uint32_t *record, uint32_t *pos, uint32_t *strand,
+                         uint32_t *dist, uint32_t *end, uint32_t *mismatch, uint32_t *gaps)
+{
+    if (!h) raise(SW_ERR_VALUE, "oligo hits: a NULL handle");
+    if (!h->has_sites) raise(SW_ERR_VALUE, "oligo hits: these hits were made without the site list");
+    const uint64_t n = h->n_list, cells = h->nq * h->n_asm;
+    if (!cell_offsets || (n && (!oligo || !assembly || !record || !pos || !strand))) raise(SW_ERR_VALUE, "oligo hits: a NULL handle or array");
+    require_device(h->device, "the oligo hits");
+    std::vector<uint32_t> counts(cells);
+    if (cells) SW_HIP(hipMemcpy(counts.data(), h->field[0].p, cells * 4, hipMemcpyDeviceToHost));
+    cell_offsets[0] = 0;
+    for (uint64_t c = 0; c < cells; ++c) cell_offsets[c + 1] = cell_offsets[c] + counts[c];
+    if (cell_offsets[cells] != n) raise(SW_ERR_RUNTIME, "internal error: the cells' site counts do not add up to the list");
+    if (!n) return;
+    std::vector<uint64_t> keys(n);
+    SW_HIP(hipMemcpy(keys.data(), h->keys.p, n * 8, hipMemcpyDeviceToHost));
+    SW_HIP(hipMemcpy(assembly, h->s_asm.p, n * 4, hipMemcpyDeviceToHost));
+    SW_HIP(hipMemcpy(record, h->s_rec.p, n * 4, hipMemcpyDeviceToHost));
+    SW_HIP(hipMemcpy(pos, h->s_pos.p, n * 4, hipMemcpyDeviceToHost));
+    for (uint64_t i = 0; i < n; ++i) {
+        uint32_t q, len_off, x, g;
+        if (h->max_edits < 0) {
+            q = (uint32_t)(keys[i] >> OL_SITE_Q_SHIFT);
+            len_off = 0;
+            x = (uint32_t)keys[i] & 15;
+            g = 0;
+        } else {
+            const uint32_t d = (uint32_t)h->max_edits, over = (uint32_t)(keys[i] >> 5) & 15, code = (uint32_t)keys[i] & 15;
+            q = (uint32_t)(keys[i] >> OLE_SITE_Q_SHIFT);
+            len_off = over - d;   // (modulo 2^32: it is added to pos + L)
+            x = code % 5;
+            g = (over > d ? over - d : d - over) + 2 * (code / 5);
+        }
+        oligo[i] = q;
+        strand[i] = (uint32_t)(keys[i] >> 4) & 1;
+        if (dist) dist[i] = x + g;
+        if (end) end[i] = pos[i] + h->lens[q] + len_off;
+        if (mismatch) mismatch[i] = x;
+        if (gaps) gaps[i] = g;
+    }
+}
+
 int sw_oligos_sites(const sw_oligos *h, uint64_t *cell_offsets, uint32_t *oligo, uint32_t *assembly, uint32_t *record, uint32_t *pos, uint32_t *strand,
                     uint32_t *mm)
 {
     return guarded([&] {
+        if (h && h->n_list && !mm) raise(SW_ERR_VALUE, "oligo hits: a NULL handle or array");
+        site_columns(h, cell_offsets, oligo, assembly, record, pos, strand, mm, nullptr, nullptr, nullptr);
+    });
+}
+
+int sw_oligos_sites_edit(const sw_oligos *h, uint64_t *cell_offsets, uint32_t *oligo, uint32_t *assembly, uint32_t *record, uint32_t *pos, uint32_t *strand,
+                         uint32_t *end, uint32_t *mismatch, uint32_t *gaps)
+{
+    return guarded([&] {
+        if (h && h->n_list && (!end || !mismatch || !gaps)) raise(SW_ERR_VALUE, "oligo hits: a NULL handle or array");
+        site_columns(h, cell_offsets, oligo, assembly, record, pos, strand, nullptr, end, mismatch, gaps);
+    });
+}
+
+int sw_batch_oligo_hits_edit(const sw_batch *batch, const uint64_t *offsets, const char *blob, uint64_t n_oligos, uint64_t max_edits, uint64_t three_prime,
+                             int want_sites, void *stream, sw_oligos **out)
+{
+    return guarded([&] {
+        const uint32_t lmin = check_oligos(offsets, blob, n_oligos, 0, three_prime);
+        check_edits(lmin, max_edits, three_prime);
+        if (!batch || !out) raise(SW_ERR_VALUE, "oligo hits: a NULL handle or array");
+        require_device(batch->device, "the batch");
+        StreamScope scope((hipStream_t)stream);
+        std::unique_ptr<sw_oligos> o(new sw_oligos);
+        o->device = batch->device;
+        batch_oligo_edit(*batch, offsets, blob, n_oligos, lmin, (uint32_t)max_edits, (uint32_t)three_prime, want_sites != 0, (hipStream_t)stream, *o);
+        *out = o.release();
+    });
+}
+
+int sw_oligos_max_edits(const sw_oligos *h, int64_t *max_edits)
+{
+    return guarded([&] {
         if (!h) raise(SW_ERR_VALUE, "oligo hits: a NULL handle");
-        if (!h->has_sites) raise(SW_ERR_VALUE, "oligo hits: these hits were made without the site list");
-        const uint64_t n = h->n_list, cells = h->nq * h->n_asm;
-        if (!cell_offsets || (n && (!oligo || !assembly || !record || !pos || !strand || !mm))) raise(SW_ERR_VALUE, "oligo hits: a NULL handle or array");
-        require_device(h->device, "the oligo hits");
-        std::vector<uint32_t> counts(cells);
-        if (cells) SW_HIP(hipMemcpy(counts.data(), h->field[0].p, cells * 4, hipMemcpyDeviceToHost));
-        cell_offsets[0] = 0;
-        for (uint64_t c = 0; c < cells; ++c) cell_offsets[c + 1] = cell_offsets[c] + counts[c];
-        if (cell_offsets[cells] != n) raise(SW_ERR_RUNTIME, "internal error: the cells' site counts do not add up to the list");
-        if (!n) return;
-        std::vector<uint64_t> keys(n);
-        SW_HIP(hipMemcpy(keys.data(), h->keys.p, n * 8, hipMemcpyDeviceToHost));
-        SW_HIP(hipMemcpy(assembly, h->s_asm.p, n * 4, hipMemcpyDeviceToHost));
-        SW_HIP(hipMemcpy(record, h->s_rec.p, n * 4, hipMemcpyDeviceToHost));
-        SW_HIP(hipMemcpy(pos, h->s_pos.p, n * 4, hipMemcpyDeviceToHost));
-        for (uint64_t i = 0; i < n; ++i) {
-            oligo[i] = (uint32_t)(keys[i] >> OL_SITE_Q_SHIFT);
-            strand[i] = (uint32_t)(keys[i] >> 4) & 1;
-            mm[i] = (uint32_t)keys[i] & 15;
-        }
+        if (max_edits) *max_edits = h->max_edits;
+    });
+}
+
+int sw_oligos_edit_stats(const sw_oligos *h, uint64_t *counters, double *ms)
+{
+    return guarded([&] {
+        if (!h) raise(SW_ERR_VALUE, "oligo hits: a NULL handle");
+        if (counters) memcpy(counters, h->edit_counters, sizeof h->edit_counters);
+        if (ms) *ms = h->resolve_ms;
     });
 }
 

@@ -340,7 +340,7 @@ class Batch:
         check(fn(self._h, _ptr(offs), blob, c_u64(nq), c_u64(int(kmerlen)), ctypes.byref(h)))
         return BestHits(h, aligned=bool(align))
 
-    def oligo_hits(self, oligos, max_mismatch: int = 0, three_prime: int = 0, sites: bool = False, stream: int = 0) -> "OligoHits":
+    def oligo_hits(self, oligos, max_mismatch: int = 0, three_prime: int = 0, sites: bool = False, stream: int = 0, max_edits=None) -> "OligoHits":
         """Every place in every assembly where an oligo (a list of ``str`` or ``bytes``: primers, probes) binds with at most
         ``max_mismatch`` mismatches, on either strand -- exhaustively, every window of the batch against every oligo, no seed
         (csrc/oligo.hip).  An oligo is 8..32 letters in either case: ``ACGT``, ``U`` (= T) or an IUPAC code
@@ -348,14 +348,25 @@ class Batch:
         inside one valid run of a record, ``mm`` the number of its bases outside the set they face; a hit has ``mm <= max_mismatch``
         (0..8, below the shortest oligo) and no mismatch among the ``three_prime`` (0..8) bases at the oligo's 3' end.  An oligo that
         equals its reverse complement hits twice at one place.  ``sites=True`` also keeps the list of all hits.  Not BLAST and not a
-        thermodynamic model: no Tm, no dG, no e-values.  ValueError for anything else, before a device is touched."""
+        thermodynamic model: no Tm, no dG, no e-values.  ValueError for anything else, before a device is touched.
+
+        ``max_edits`` (0..4, ``max_edits + three_prime`` below the shortest oligo, ``max_mismatch`` left at 0) searches by unit-cost
+        edit distance instead, so that a site with a bulge of a base or two is found: an end ``e`` of a
+        valid run is a site iff the oligo without its ``three_prime`` last letters aligns to some text that ends ``three_prime``
+        bases before ``e`` within ``max_edits`` edits, those last bases match exactly, and no end within ``max_edits`` before it is
+        as good nor one within ``max_edits`` after it better.  A site then has ``pos``, ``end``, ``dist``, ``mismatch`` and
+        ``gaps`` from the canonical alignment.  ``max_edits=0`` gives the sites of ``max_mismatch=0``."""
         from .oligos import check_oligos
-        qs = check_oligos(oligos, max_mismatch, three_prime)
+        qs = check_oligos(oligos, max_mismatch, three_prime, max_edits)
         offs = np.zeros(len(qs) + 1, np.uint64)
         np.cumsum([len(q) for q in qs], out=offs[1:])
         h = c_vp()
-        check(lib.sw_batch_oligo_hits(self._h, _ptr(offs), b"".join(qs), c_u64(len(qs)), c_u64(int(max_mismatch)), c_u64(int(three_prime)),
-                                      ctypes.c_int(1 if sites else 0), c_vp(stream), ctypes.byref(h)))
+        if max_edits is None:
+            check(lib.sw_batch_oligo_hits(self._h, _ptr(offs), b"".join(qs), c_u64(len(qs)), c_u64(int(max_mismatch)), c_u64(int(three_prime)),
+                                          ctypes.c_int(1 if sites else 0), c_vp(stream), ctypes.byref(h)))
+        else:
+            check(lib.sw_batch_oligo_hits_edit(self._h, _ptr(offs), b"".join(qs), c_u64(len(qs)), c_u64(int(max_edits)), c_u64(int(three_prime)),
+                                               ctypes.c_int(1 if sites else 0), c_vp(stream), ctypes.byref(h)))
         return OligoHits(h, [len(q) for q in qs], bool(sites))
 
     def fetch(self, intervals, stats: bool = False):
@@ -1162,6 +1173,7 @@ class KmerProfile:
 
 
 SITE_FIELDS = ("oligo", "assembly", "record", "pos", "strand", "mm")
+SITE_FIELDS_EDIT = ("oligo", "assembly", "record", "pos", "strand", "end", "mismatch", "gaps")
 
 
 class OligoHits:
@@ -1170,12 +1182,19 @@ class OligoHits:
     order (mm, record, pos, strand) as ``best_mm``, ``best_record`` (global), ``best_pos`` and ``best_strand`` -- NO_HIT without a
     hit.  It has no counterpart in the reference, is not BLAST, is no thermodynamic model and fills none of ``MarkerMetrics``.  A
     single-device object on a resident batch.  ``rows`` (oligos) / ``cols`` (assemblies) are None (all), a ``(lo, hi)`` pair, a slice
-    or a range.  Made with ``sites=True`` it also holds the list of all hits."""
+    or a range.  Made with ``sites=True`` it also holds the list of all hits.
+
+    Made with ``max_edits`` a site has a ``pos``, an ``end``, a ``dist`` = ``mismatch`` + ``gaps``; the best
+    site is the least in (dist, record, pos, strand), then end, and ``best_mm`` is a ValueError: ask for ``best_dist``.  On a result
+    without it ``dist`` and ``mismatch`` are ``mm``, ``end`` is ``pos + L`` and ``gaps`` is 0."""
 
     def __init__(self, handle: c_vp, lengths, sites: bool = False):
         self._h = handle
         self.lengths = np.asarray(lengths, np.uint32)
         self._sites = sites
+        v = ctypes.c_int64()
+        check(lib.sw_oligos_max_edits(self._h, ctypes.byref(v)))
+        self.max_edits = None if v.value < 0 else int(v.value)
 
     def sizes(self):
         """(oligos, assemblies, max_mismatch, three_prime)"""
@@ -1195,7 +1214,22 @@ class OligoHits:
         return self._block(0, rows, cols)
 
     def best_mm(self, rows=None, cols=None) -> np.ndarray:
+        if self.max_edits is not None:
+            raise ValueError("these oligo hits were made with max_edits: ask for best_dist, best_mismatch and best_gaps")
         return self._block(1, rows, cols)
+
+    def best_dist(self, rows=None, cols=None) -> np.ndarray:
+        """uint32[rows, cols]: the best site's edit distance (without ``max_edits``: its mismatches); NO_HIT without a site."""
+        return self._block(1, rows, cols)
+
+    def best_end(self, rows=None, cols=None) -> np.ndarray:
+        return self._block(5, rows, cols)
+
+    def best_mismatch(self, rows=None, cols=None) -> np.ndarray:
+        return self._block(6, rows, cols)
+
+    def best_gaps(self, rows=None, cols=None) -> np.ndarray:
+        return self._block(7, rows, cols)
 
     def best_record(self, rows=None, cols=None) -> np.ndarray:
         return self._block(2, rows, cols)
@@ -1208,36 +1242,50 @@ class OligoHits:
 
     def sites(self) -> dict:
         """Every hit, ascending by (oligo, assembly, record, pos, strand), as parallel uint32 arrays ``oligo``, ``assembly``,
-        ``record``, ``pos``, ``strand``, ``mm``; ``cell_offsets`` (uint64[oligos * assemblies + 1]) bounds the hits of every pair."""
+        ``record``, ``pos``, ``strand``, ``end``, ``dist``, ``mismatch``, ``gaps`` -- and ``mm`` on a result without ``max_edits``;
+        with it the order is (oligo, assembly, record, pos, end, strand).  ``cell_offsets`` (uint64[oligos * assemblies + 1]) bounds
+        the hits of every pair."""
         if not self._sites:
             raise ValueError("these oligo hits were made without sites=True")
         nq, na, _, _ = self.sizes()
         n = c_u64()
         check(lib.sw_oligos_sites_size(self._h, ctypes.byref(n)))
         offs = np.empty(nq * na + 1, np.uint64)
-        cols = [np.empty(n.value, np.uint32) for _ in SITE_FIELDS]
-        check(lib.sw_oligos_sites(self._h, _ptr(offs), *[_ptr(a) if n.value else None for a in cols]))
-        out = dict(zip(SITE_FIELDS, cols))
+        if self.max_edits is None:     # the call and the columns of section 3.2j; the four new ones follow from them
+            cols = [np.empty(n.value, np.uint32) for _ in SITE_FIELDS]
+            check(lib.sw_oligos_sites(self._h, _ptr(offs), *[_ptr(a) if n.value else None for a in cols]))
+            out = dict(zip(SITE_FIELDS, cols))
+            out.update(end=out["pos"] + self.lengths[out["oligo"]], dist=out["mm"].copy(), mismatch=out["mm"].copy(), gaps=np.zeros(n.value, np.uint32))
+        else:
+            cols = [np.empty(n.value, np.uint32) for _ in SITE_FIELDS_EDIT]
+            check(lib.sw_oligos_sites_edit(self._h, _ptr(offs), *[_ptr(a) if n.value else None for a in cols]))
+            out = dict(zip(SITE_FIELDS_EDIT, cols))
+            out["dist"] = out["mismatch"] + out["gaps"]
         out["cell_offsets"] = offs
         return out
 
     def intervals(self) -> np.ndarray:
-        """INTERVAL_DTYPE ``(record, pos, pos + L)`` of every hit, in the list's order, as :meth:`Batch.fetch` takes them (the text
-        of a strand-1 hit faces the oligo's reverse complement)."""
+        """INTERVAL_DTYPE ``(record, pos, end)`` of every hit, in the list's order, as :meth:`Batch.fetch` takes them (the text
+        of a strand-1 hit faces the oligo's reverse complement); ``end`` is ``pos + L`` unless the site has gaps."""
         S = self.sites()
         iv = np.empty(len(S["oligo"]), INTERVAL_DTYPE)
-        iv["record"], iv["start"], iv["stop"] = S["record"], S["pos"], S["pos"] + self.lengths[S["oligo"]]
+        iv["record"], iv["start"], iv["stop"] = S["record"], S["pos"], S["end"]
         return iv
 
     def stats(self) -> dict:
         """``windows`` (window ends scanned, summed over the passes), ``passes`` (groups of oligos), ``chunks`` (of assemblies),
         ``launches``, ``hits``, ``buffer_doublings``, ``chunk_splits``, ``comparisons`` (window x oligo x strand), ``scan_ms`` and
-        ``order_ms`` (HIP events)."""
+        ``order_ms`` (HIP events); ``dp_steps`` (steps of the bit-vector column, an upper bound), ``candidates`` (resolved by the
+        alignment kernel) and ``resolve_ms`` -- zeros without ``max_edits``; with it ``scan_ms`` excludes ``resolve_ms``."""
         c = (c_u64 * 8)()
         ms = (ctypes.c_double * 2)()
         check(lib.sw_oligos_stats(self._h, c, ms))
         d = dict(zip(("windows", "passes", "chunks", "launches", "hits", "buffer_doublings", "chunk_splits", "comparisons"), (int(x) for x in c)))
         d.update(scan_ms=ms[0], order_ms=ms[1])
+        c2 = (c_u64 * 2)()
+        ms2 = ctypes.c_double()
+        check(lib.sw_oligos_edit_stats(self._h, c2, ctypes.byref(ms2)))
+        d.update(dp_steps=int(c2[0]), candidates=int(c2[1]), resolve_ms=ms2.value)
         return d
 
     def close(self) -> None:

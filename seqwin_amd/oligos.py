@@ -9,15 +9,17 @@ from __future__ import annotations
 
 import numpy as np
 
-MIN_LEN, MAX_LEN, MAX_OLIGOS, MAX_MISMATCH, MAX_THREE_PRIME = 8, 32, 4096, 8, 8
+MIN_LEN, MAX_LEN, MAX_OLIGOS, MAX_MISMATCH, MAX_THREE_PRIME, MAX_EDITS = 8, 32, 4096, 8, 8, 4
 IUPAC = {"A": "A", "C": "C", "G": "G", "T": "T", "U": "T", "R": "AG", "Y": "CT", "S": "CG", "W": "AT", "K": "GT", "M": "AC", "B": "CGT",
          "D": "AGT", "H": "ACT", "V": "ACG", "N": "ACGT"}
 AMPLICON_FIELDS = ("pair", "assembly", "record", "start", "end", "orientation", "mm_f", "mm_r")
 
 
-def check_oligos(oligos, max_mismatch: int = 0, three_prime: int = 0):
+def check_oligos(oligos, max_mismatch: int = 0, three_prime: int = 0, max_edits=None):
     """The oligos as a list of ``bytes``, after the checks the library makes again: 1..4096 oligos of 8..32 IUPAC letters (either
-    case, ``U`` = ``T``), ``max_mismatch`` in 0..8 and below the shortest oligo, ``three_prime`` in 0..8.  ValueError otherwise."""
+    case, ``U`` = ``T``), ``max_mismatch`` in 0..8 and below the shortest oligo, ``three_prime`` in 0..8; with ``max_edits`` (the
+    search with indels): 0..4, ``max_edits + three_prime`` below the shortest oligo, and ``max_mismatch``
+    must be 0.  ValueError otherwise."""
     if isinstance(oligos, (str, bytes, bytearray)):
         raise ValueError("oligos must be a list of str or bytes, not one string")
     out = []
@@ -39,6 +41,13 @@ def check_oligos(oligos, max_mismatch: int = 0, three_prime: int = 0):
         raise ValueError(f"max_mismatch must lie in 0..{MAX_MISMATCH} and below the shortest oligo's {shortest} letters (got {max_mismatch})")
     if int(three_prime) != three_prime or not 0 <= three_prime <= MAX_THREE_PRIME:
         raise ValueError(f"three_prime must lie in 0..{MAX_THREE_PRIME} (got {three_prime})")
+    if max_edits is not None:
+        if max_mismatch:
+            raise ValueError("max_edits and a non-zero max_mismatch exclude each other")
+        if int(max_edits) != max_edits or not 0 <= max_edits <= MAX_EDITS:
+            raise ValueError(f"max_edits must lie in 0..{MAX_EDITS} (got {max_edits})")
+        if max_edits + three_prime >= shortest:
+            raise ValueError(f"max_edits + three_prime must lie below the shortest oligo's {shortest} letters (got {max_edits} + {three_prime})")
     return out
 
 
@@ -52,7 +61,8 @@ def amplicons(hits, lengths, pairs, min_len: int, max_len: int, n_assemblies=Non
     record there are two orientations: ``+`` (0), a hit of f on strand 0 at ``pf`` and a hit of r on strand 1 at ``pr >= pf``, product
     ``[pf, pr + L_r)``; ``-`` (1), a hit of r on strand 0 at ``pr`` and a hit of f on strand 1 at ``pf >= pr``, product ``[pr, pf +
     L_f)``.  A product is kept iff ``min_len <= end - start <= max_len``; every combination counts; with ``f == r`` only ``+`` is
-    counted; a product may span invalid bases.  Returns ``(products, n_amplicons)``: a dict of arrays ``pair``, ``assembly``,
+    counted; a product may span invalid bases.  Where the sites carry an ``end`` (a search with ``max_edits``: a site with a bulge is
+    not L bases long) the product ends at the last site's ``end`` and ``mm_f`` / ``mm_r`` are the sites' ``dist``.  Returns ``(products, n_amplicons)``: a dict of arrays ``pair``, ``assembly``,
     ``record``, ``start``, ``end``, ``orientation``, ``mm_f``, ``mm_r``, ordered by those fields in that order, and
     ``n_amplicons[n_pairs, n_assemblies]`` (uint32).  ``n_assemblies`` is read from ``hits`` unless given."""
     S = _sites(hits)
@@ -67,7 +77,8 @@ def amplicons(hits, lengths, pairs, min_len: int, max_len: int, n_assemblies=Non
     if min_len > max_len:
         raise ValueError(f"min_len {min_len} exceeds max_len {max_len}")
     oligo, strand = S["oligo"].astype(np.int64), S["strand"].astype(np.int64)
-    rec, pos, asm, mm = S["record"].astype(np.int64), S["pos"].astype(np.int64), S["assembly"].astype(np.int64), S["mm"].astype(np.int64)
+    rec, pos, asm, mm = S["record"].astype(np.int64), S["pos"].astype(np.int64), S["assembly"].astype(np.int64), (S["mm"] if "mm" in S else S["dist"]).astype(np.int64)
+    site_end = S["end"].astype(np.int64) if "end" in S else pos + lengths[oligo]
     cols = []
 
     def side(q, s):
@@ -78,16 +89,17 @@ def amplicons(hits, lengths, pairs, min_len: int, max_len: int, n_assemblies=Non
         """every (site of `first` on strand 0, site of `last` on strand 1) of one record with a product length inside the bounds"""
         if not len(first) or not len(last):
             return
+        slack = MAX_EDITS if "end" in S else 0     # a site spans len_last -+ slack bases; the bounds are applied to the true ends below
         key_last = (rec[last] << 32) + pos[last]   # pr in [pf + max(min_len - L, 0), pf + max_len - L] of the same record
-        lo = np.searchsorted(key_last, (rec[first] << 32) + pos[first] + max(min_len - len_last, 0), "left")
-        hi = np.searchsorted(key_last, (rec[first] << 32) + np.minimum(pos[first] + max_len - len_last, 0xFFFFFFFF), "right")
+        lo = np.searchsorted(key_last, (rec[first] << 32) + pos[first] + max(min_len - len_last - slack, 0), "left")
+        hi = np.searchsorted(key_last, (rec[first] << 32) + np.minimum(pos[first] + max_len - len_last + slack, 0xFFFFFFFF), "right")
         n = np.maximum(hi - lo, 0)
         a = np.repeat(np.arange(len(first)), n)
         b = np.concatenate([np.arange(x, y) for x, y in zip(lo, hi) if y > x]) if n.sum() else np.zeros(0, np.int64)
         i, j = first[a], last[b]
-        keep = pos[j] >= pos[i]
+        keep = (pos[j] >= pos[i]) & (site_end[j] - pos[i] >= min_len) & (site_end[j] - pos[i] <= max_len)
         i, j = i[keep], j[keep]
-        start, end = pos[i], pos[j] + len_last
+        start, end = pos[i], site_end[j]
         mf, mr = (mm[i], mm[j]) if f_is_first else (mm[j], mm[i])
         cols.append(np.stack([np.full(len(i), pi), asm[i], rec[i], start, end, np.full(len(i), orientation), mf, mr], 1))
 
@@ -105,9 +117,13 @@ def amplicons(hits, lengths, pairs, min_len: int, max_len: int, n_assemblies=Non
 
 def oligo_summary(hits, n_tar: int) -> dict:
     """Per oligo, over the targets (assemblies below ``n_tar``) and the others: ``f_tar`` / ``f_neg``, the fraction of them with a
-    hit (``nan`` for an empty side), and ``mean_best_mm_tar``, the mean ``best_mm`` over the targets with a hit (``nan`` without one)."""
+    hit (``nan`` for an empty side), and ``mean_best_mm_tar``, the mean ``best_mm`` over the targets with a hit (``nan`` without one);
+    on a result with ``max_edits`` it is the mean ``best_dist``."""
     n = np.asarray(hits.n_sites() if hasattr(hits, "n_sites") else hits["n_sites"])
-    best = np.asarray(hits.best_mm() if hasattr(hits, "best_mm") else hits["best_mm"])
+    if hasattr(hits, "best_dist"):
+        best = np.asarray(hits.best_dist())
+    else:
+        best = np.asarray(hits["best_mm"] if "best_mm" in hits else hits["best_dist"])
     if not 0 <= n_tar <= n.shape[1]:
         raise ValueError(f"n_tar {n_tar} lies outside the {n.shape[1]} assemblies")
     has = n > 0
