@@ -76,6 +76,55 @@ def assert_list(wide: dict, shard: dict, fields, n_rows: int, n_cols: int, c0: i
     assert np.array_equal(w_cnt[:, c0:c0 + s_cols], s_cnt), (what, "cell_offsets")
 
 
+def rows_of(lst: dict, fields, keep=None) -> list:
+    """The entries of a list as tuples over ``fields``, in the list's order; ``keep``: a mask over the entries."""
+    cols = [np.asarray(lst[f]).astype(np.int64) for f in fields]
+    if keep is not None:
+        cols = [c[keep] for c in cols]
+    return list(zip(*(c.tolist() for c in cols)))
+
+
+# ---- the oligo search with indels on excerpts ----------------------------------------------------------------------------------------
+# How far a site must lie from an excerpt's edge for the excerpt to decide it as the record does.  By tests/tools/oligo_edit_host.py
+# an end e is a site by the values D(e') of the ends e - d <= e' <= e + d, and D(e') <= d is decided by the text an alignment of the
+# oligo with at most d edits can face: the L + d bases before e'.  So the site [pos, e) on strand 0 is decided by the bases
+# [e - d - (L + d), e + d) -- and e > pos, so an edge L + 2 d bases or more before pos and d or more behind e changes nothing: a cut
+# text only takes alignments away (row 0 is free at every column, so the boundary column Dm[i][0] = i offers nothing the record does
+# not), every value <= d keeps its alignment and with it its value, every other value stays above d, and the traceback compares only
+# values <= d.  Strand 1 is the same on the reverse complement, with the sides exchanged.  L <= 32 and d <= 4 (OLE_MAX_EDITS): 32 +
+# 2 * 4, and 4 to spare.  An edge of the excerpt that is the record's own edge needs no margin: the run ends there on the device too.
+EDIT_MARGIN = 32 + 2 * 4 + 4
+
+
+def interior(lo: int, hi: int, rec_len: int, margin: int = EDIT_MARGIN):
+    """[a, z) of the excerpt [lo, hi) of a record: the sites inside it are decided by the excerpt alone."""
+    assert 0 <= lo < hi <= rec_len
+    return (lo if lo == 0 else lo + margin), (hi if hi == rec_len else hi - margin)
+
+
+def bulge_at(text: bytes, lo: int = 4) -> int:
+    """The index nearest the middle of ``text`` (at least ``lo`` + 1 letters from either end) whose base differs from both of its
+    neighbours: deleting it, or inserting a fourth base in front of it, is one gap column in every optimal alignment's count."""
+    n = len(text)
+    for i in sorted(range(lo + 1, n - lo - 1), key=lambda i: (abs(i - n // 2), i)):
+        if text[i] != text[i - 1] and text[i] != text[i + 1]:
+            return i
+    raise AssertionError("no base that differs from both neighbours")
+
+
+def deleted(text: bytes) -> bytes:
+    """``text`` without the base at :func:`bulge_at`"""
+    i = bulge_at(text)
+    return bytes(text[:i] + text[i + 1:])
+
+
+def inserted(text: bytes) -> bytes:
+    """``text`` with a base that neither neighbour is in front of :func:`bulge_at`"""
+    i = bulge_at(text)
+    new = next(c for c in b"ACGT" if c not in (text[i - 1], text[i]))
+    return bytes(text[:i]) + bytes([new]) + bytes(text[i:])
+
+
 def has_entry(lst: dict, **want) -> bool:
     """Whether a list holds an entry with these values."""
     m = None
