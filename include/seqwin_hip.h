@@ -737,8 +737,8 @@ int sw_windows_stats(const sw_windows *w, uint64_t *counters, double *ms);
 void sw_windows_free(sw_windows *w);
 
 /* ---- oligo search: every place where a primer or probe binds with at most d mismatches, on either strand (csrc/oligo.hip) ----
- * None of this has a counterpart in the reference.  It is NOT BLAST and NOT a thermodynamic model: no Tm, no dG, no e-values; one
- * exactly specified quantity, Hamming distance under IUPAC sets, over EVERY window of the resident batch -- no seed is needed, so no
+ * None of this has a counterpart in the reference.  It is NOT BLAST (no e-values) and a site is not defined by a thermodynamic
+ * model (that is an addition behind the hit: sw_batch_oligo_hits_thermo below); one exactly specified quantity, Hamming distance under IUPAC sets, over EVERY window of the resident batch -- no seed is needed, so no
  * site is missed.  DESIGN.md section 3.2j is the specification, tests/tools/oligo_host.py restates it.
  * An oligo is 8..32 letters in either case: A C G T, U (= T) or an IUPAC code R Y S W K M B D H V N; every position is a set of
  * bases.  P0 is the oligo, P1 its reverse complement (the sets complemented, the order reversed).  A site (oligo, strand s, record,
@@ -793,6 +793,31 @@ int sw_oligos_sites_edit(const sw_oligos *h, uint64_t *cell_offsets, uint32_t *o
  * L + 3 max_edits - 1 steps more than it has ends, per oligo and strand), candidates resolved }; ms[1] = { the resolve kernel };
  * zeros for a Hamming result.  With max_edits sw_oligos_stats' scan time excludes the resolve kernel. */
 int sw_oligos_edit_stats(const sw_oligos *h, uint64_t *counters, double *ms);
+/* ---- oligo search with a nearest-neighbour model (csrc/oligo.hip; tests/tools/oligo_thermo_host.py restates
+ * it) ----
+ * The hits of sw_batch_oligo_hits, and per hit the sums of the CALLER'S integer tables.  Base codes A=0 C=1 G=2 T=3.  stack is
+ * int16[3][4][4][4][4], planes dh (100 cal/mol), ds (0.1 cal/(K mol)), dg (cal/mol), index [x1][x2][y1][y2]: x1 x2 two consecutive
+ * oligo bases 5'->3', y1 y2 the bases of the bound strand that face them (y1 pairs with x1).  end is int16[3][2][4][4]: the terminal
+ * pair [x][y] at the oligo's 5' end (0) and 3' end (1).  init is int32[3].  For a hit with window text t_0..t_{L-1}: strand 0
+ * y_i = 3 - t_{i-1}, strand 1 y_i = t_{L-i}; x_i = 3 - y_i where the oligo's set at i holds it, else the set's least member;
+ * (dh, ds, dg) = init + end[0][x_1][y_1] + end[1][x_L][y_L] + the sum of stack[x_i][x_i+1][y_i][y_i+1], in int32.  Per cell: n_stable,
+ * the hits with dg <= max_dg, and the MOST STABLE hit, least in (dg, record, pos, strand) among all hits.  Nothing is multiplied by
+ * a temperature and no Tm is formed on the device; bulges (max_edits), dimers, hairpins, dangling ends and salt are out of scope. */
+/* (no counterpart in the reference)  As sw_batch_oligo_hits, with the model.  Every dg entry and init[2] must satisfy |v| <= 15000
+ * (the most stable site's key relies on it): SW_ERR_VALUE otherwise, before a device is touched.  no_threshold != 0: every hit counts
+ * as stable and max_dg is ignored. */
+int sw_batch_oligo_hits_thermo(const sw_batch *batch, const uint64_t *offsets, const char *blob, uint64_t n_oligos, uint64_t max_mismatch,
+                               uint64_t three_prime, int want_sites, void *stream, const int16_t *stack, const int16_t *end,
+                               const int32_t *init, int64_t max_dg, int no_threshold, sw_oligos **out);
+/* (no counterpart in the reference)  sw_oligos_block for the model's fields, 4 bytes an entry: 0 n_stable (uint32); of the most
+ * stable hit 1 stable_dg, 2 stable_dh, 3 stable_ds (int32; INT32_MIN without a hit), 4 stable_record, 5 stable_pos, 6 stable_strand,
+ * 7 stable_mm (uint32; 0xFFFFFFFF without a hit).  This and the two below: SW_ERR_VALUE for a result made without a model. */
+int sw_oligos_thermo_block(const sw_oligos *h, uint64_t field, uint64_t r0, uint64_t r1, uint64_t c0, uint64_t c1, void *out);
+/* (no counterpart in the reference)  dh, ds, dg of every entry of the site list, parallel to sw_oligos_sites' columns. */
+int sw_oligos_sites_thermo(const sw_oligos *h, int32_t *dh, int32_t *ds, int32_t *dg);
+/* (no counterpart in the reference)  *stable_hits = the sum of n_stable; ms[2] = { the kernel of the most stable sites' fields, the
+ * kernel of the list's sums } (HIP events).  sw_oligos_stats' scan time excludes the first. */
+int sw_oligos_thermo_stats(const sw_oligos *h, uint64_t *stable_hits, double *ms);
 /* (no counterpart in the reference) */
 void sw_oligos_free(sw_oligos *h);
 

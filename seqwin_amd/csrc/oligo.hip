@@ -1,8 +1,9 @@
 // oligo.hip -- every place in every assembly of a resident batch where a short oligo (a primer, a probe) binds with at most d
 // mismatches, on either strand: Hamming distance under IUPAC sets, exhaustive -- every window of the batch against every oligo.
 //
-// It has no counterpart in the reference, it is NOT BLAST and NOT a thermodynamic model (no Tm, no dG, no e-values), and it fills
-// none of MarkerMetrics.  DESIGN.md section 3.2j is the specification; tests/tools/oligo_host.py restates it twice.
+// It has no counterpart in the reference, it is NOT BLAST (no e-values), and it fills none of MarkerMetrics.  DESIGN.md section 3.2j
+// is the specification; tests/tools/oligo_host.py restates it twice.  A site is a Hamming site; what a caller's nearest-neighbour
+// model says about it is an addition behind the hit (below, section 3.2o) -- integers on the caller's tables, no Tm on the device.
 //
 //   host           an oligo of L = 8..32 letters is L sets of bases.  Per oligo and strand one row of the pattern table (8 words):
 //                  four MISMATCH planes -- bit t of plane b is set iff base b is NOT in the set that faces the text base t places
@@ -19,6 +20,14 @@
 //                  the site buffer (wave_append).  All three are order-independent.
 //   k_ol_resolve   the best site's key -> mm, record, pos, strand of a cell
 //   k_ol_decode    a sorted site key -> assembly, record, pos
+// With a thermodynamic model (tests/tools/oligo_thermo_host.py; oligo_thermo_core.hpp holds the site sum):
+//   k_ol_scan<true>     the same walk; behind the candidate ballot, where mm is recomputed per hit anyway, it also sums the site's
+//                       dg, counts it where dg <= max_dg (atomicAdd) and offers it as the most stable site (a second 64-bit
+//                       atomicMin).  The tables (1.6 KB, divergent indices) are read from global memory through L1, not staged
+//                       in LDS: hits are rare and k_ol_scan<false> must stay as it is.  No A/B of the two exists.
+//   k_ol_thermo_best    the stable key -> the seven stable fields of a cell; it re-reads the window for dh, ds and mm
+//   k_ol_thermo_sites   a sorted site key -> dh, ds, dg of the site; it re-reads L bases of the packed batch
+// k_ol_scan<false> is the kernel without a model: a call without one launches what it launched before and allocates nothing more.
 // Oligos are taken in groups (a pass over the batch each), assemblies in chunks bounded by the site buffer: a chunk that overflows
 // is redone in two halves, one assembly that overflows has the buffer doubled -- as hits.hip treats its key buffer.
 //
@@ -34,6 +43,7 @@
 //   k_ole_best     the best site's key -> the seven best fields of a cell;  k_ole_decode  a sorted site key -> assembly, record, pos
 #include "screen_core.hpp"
 #include "oligo_edit_core.hpp"
+#include "oligo_thermo_core.hpp"
 
 namespace sw {
 namespace {
@@ -47,6 +57,10 @@ constexpr uint64_t OL_MAX_SITES = 1ull << 32;
 constexpr unsigned long long OL_NONE = ~0ull;
 // best-site key: mm << 58 | base index << 1 | strand; site key: oligo << 48 | base index << 5 | strand << 4 | mm
 constexpr uint32_t OL_BEST_MM_SHIFT = 58, OL_SITE_Q_SHIFT = 48, OL_SITE_IDX_SHIFT = 5;
+// stable-site key: (dg + 2^19) << 44 | base index << 1 | strand -- 20 + 43 + 1 bits
+constexpr uint32_t OL_STABLE_DG_SHIFT = 44;
+static_assert(OL_MAX_BASES == 1ull << (OL_STABLE_DG_SHIFT - 1), "the stable key keeps the base index below the biased dg");
+static_assert((OL_MAX_LEN + 2) * olt::MAX_DG < olt::DG_BIAS, "the biased dg of the longest oligo is positive and has 20 bits");
 
 typedef const __attribute__((address_space(4))) uint32_t *ol_table_t;   // constant address space: uniform reads are scalar loads
 
@@ -61,6 +75,14 @@ struct ScanArgs {
     unsigned long long *buf;         // site keys of the chunk (nullptr: no list is wanted; the cursor still counts)
     unsigned long long cap;
     unsigned long long *cursor;      // sites appended (above cap: the chunk overflowed, it is redone)
+};
+
+// what k_ol_scan<true> takes besides: the model and the cells it fills
+struct ThermoScanArgs : ScanArgs {
+    olt::Tables model;               // (device pointers)
+    int32_t max_dg;                  // a hit with dg <= max_dg is stable (INT32_MAX: every hit)
+    uint32_t *n_stable;              // [n_oligos][n_asm]
+    unsigned long long *stable;      // [oligos of the pass][n_asm]
 };
 
 // the last 32 bases a lane has read, as the plane of their low bits and the plane of their high bits; bit 0 = the last base
@@ -100,7 +122,7 @@ __device__ __forceinline__ uint32_t ol_mismatches(uint32_t lo, uint32_t hi, uint
     return ol_select(hi, ol_select(lo, n3, n2), ol_select(lo, n1, n0));
 }
 
-__global__ __launch_bounds__(KW_TPB) void k_ol_scan(ScanArgs g)
+template <bool THERMO> __global__ __launch_bounds__(KW_TPB) void k_ol_scan(typename std::conditional<THERMO, ThermoScanArgs, ScanArgs>::type g)
 {
     const uint32_t lane = threadIdx.x % KW_WAVE;
     uint32_t r, n_mine;
@@ -157,6 +179,24 @@ __global__ __launch_bounds__(KW_TPB) void k_ol_scan(ScanArgs g)
                 g.buf[w.base + w.offset + at] = ((unsigned long long)(g.q0 + q_local) << OL_SITE_Q_SHIFT) | (idx << OL_SITE_IDX_SHIFT) | (strand << 4) | mm;
             ++at;
         }
+        if constexpr (THERMO) {
+            // the model's part, hit by hit in a loop of its own: one copy of the walk over the oligo's positions, not one per place
+            // of the lane (16 copies cost 254 VGPRs).  No wave operation inside, so the lanes may leave it apart.
+            for (uint32_t rest = cand; rest; rest &= rest - 1) {
+                const uint32_t j = (uint32_t)__ffs(rest) - 1;
+                uint32_t l = lo[0], h = hi[0];
+#pragma unroll
+                for (uint32_t x = 1; x < KW_L; ++x) {
+                    l = j == x ? lo[x] : l;
+                    h = j == x ? hi[x] : h;
+                }
+                const int32_t dg = olt::site<false>(l, h, n0, n1, n2, n3, len, strand, g.model).dg;
+                const unsigned long long idx = run_base + e0 + j + 1 - len;
+                if (dg <= g.max_dg) atomicAdd(g.n_stable + (uint64_t)(g.q0 + q_local) * g.n_asm + a, 1u);
+                atomicMin(g.stable + (uint64_t)q_local * g.n_asm + a,
+                          ((unsigned long long)(uint32_t)(dg + olt::DG_BIAS) << OL_STABLE_DG_SHIFT) | (idx << 1) | strand);
+            }
+        }
     }
 }
 
@@ -198,6 +238,60 @@ __global__ __launch_bounds__(SCR_TPB) void k_ol_decode(uint64_t base, uint64_t e
     asm_out[i] = v.run_asm[r];
     rec[i] = v.run_rec[r];
     pos[i] = v.run_pos[r] + (uint32_t)(idx - v.run_base[r]);
+}
+
+struct StableFields {
+    int32_t *dg, *dh, *ds;
+    uint32_t *rec, *pos, *strand, *mm;
+};
+
+// cell i of the pass: the seven fields of its most stable site, or NO_HIT (the signed fields: INT32_MIN) without one
+__global__ __launch_bounds__(SCR_TPB) void k_ol_thermo_best(uint64_t base, uint64_t end, const unsigned long long *__restrict__ stable, uint64_t cell0, RunView v,
+                                                            const uint32_t *__restrict__ tab, uint64_t n_asm, olt::Tables model, StableFields f)
+{
+    const uint64_t i = base + (uint64_t)blockIdx.x * SCR_TPB + threadIdx.x;
+    if (i >= end) return;
+    const unsigned long long key = stable[i];
+    if (key == OL_NONE) {
+        f.dg[cell0 + i] = f.dh[cell0 + i] = f.ds[cell0 + i] = olt::NO_SUM;
+        f.rec[cell0 + i] = f.pos[cell0 + i] = f.strand[cell0 + i] = f.mm[cell0 + i] = 0xFFFFFFFFu;
+        return;
+    }
+    const uint64_t idx = (key & ((1ull << OL_STABLE_DG_SHIFT) - 1)) >> 1;
+    const uint32_t strand = (uint32_t)(key & 1);
+    const uint32_t r = ol_run_of(v.run_base, v.n_runs, idx);
+    const uint32_t *row = tab + ((i / n_asm) * 2 + strand) * OL_ROW;
+    const uint32_t n0 = row[0], n1 = row[1], n2 = row[2], n3 = row[3], len = row[5];
+    uint32_t lo, hi;
+    olt::window(v.packed, idx, len, lo, hi);   // (a site lies inside its run: [idx, idx + len) are bases of the batch)
+    const olt::Sums s = olt::site<true>(lo, hi, n0, n1, n2, n3, len, strand, model);
+    f.dg[cell0 + i] = s.dg;                    // (= the key's dg)
+    f.dh[cell0 + i] = s.dh;
+    f.ds[cell0 + i] = s.ds;
+    f.rec[cell0 + i] = v.run_rec[r];
+    f.pos[cell0 + i] = v.run_pos[r] + (uint32_t)(idx - v.run_base[r]);
+    f.strand[cell0 + i] = strand;
+    f.mm[cell0 + i] = (uint32_t)__popc(olt::mismatches(lo, hi, n0, n1, n2, n3));
+}
+
+// sorted site key i: the sums of its site.  tab holds the rows of ALL oligos of the call
+__global__ __launch_bounds__(SCR_TPB) void k_ol_thermo_sites(uint64_t base, uint64_t end, const uint64_t *__restrict__ keys, const uint32_t *__restrict__ packed,
+                                                             const uint32_t *__restrict__ tab, olt::Tables model, int32_t *__restrict__ dh,
+                                                             int32_t *__restrict__ ds, int32_t *__restrict__ dg)
+{
+    const uint64_t i = base + (uint64_t)blockIdx.x * SCR_TPB + threadIdx.x;
+    if (i >= end) return;
+    const uint64_t key = keys[i];
+    const uint64_t idx = (key & ((1ull << OL_SITE_Q_SHIFT) - 1)) >> OL_SITE_IDX_SHIFT;   // (64 bits: the batch-wide index passes 2^32)
+    const uint32_t q = (uint32_t)(key >> OL_SITE_Q_SHIFT), strand = (uint32_t)(key >> 4) & 1u;
+    const uint32_t *row = tab + ((uint64_t)q * 2 + strand) * OL_ROW;
+    const uint32_t len = row[5];
+    uint32_t lo, hi;
+    olt::window(packed, idx, len, lo, hi);
+    const olt::Sums s = olt::site<true>(lo, hi, row[0], row[1], row[2], row[3], len, strand, model);
+    dh[i] = s.dh;
+    ds[i] = s.ds;
+    dg[i] = s.dg;
 }
 
 // ---- the route with indels (section 3.2n) ---------------------------------------------------------------------------------------------
@@ -413,13 +507,42 @@ struct sw_oligos {
     double ms[2] = {};                     // scan, order
     uint64_t edit_counters[2] = {};        // sw_oligos_edit_stats: DP steps, candidates resolved
     double resolve_ms = 0;
+    // a Hamming result made with a thermodynamic model (section 3.2o); nothing of it is allocated without one
+    bool thermo = false;
+    sw::DevArray<uint32_t> n_stable;       // [nq][n_asm]
+    sw::DevArray<int32_t> stable_sum[3];   // [nq][n_asm] stable_dg, stable_dh, stable_ds
+    sw::DevArray<uint32_t> stable_at[4];   // [nq][n_asm] stable_record, stable_pos, stable_strand, stable_mm
+    sw::DevArray<int32_t> s_sum[3];        // [n_list] dh, ds, dg of the sites
+    double thermo_ms[2] = {};              // k_ol_thermo_best, k_ol_thermo_sites
 };
 
 namespace sw {
 namespace {
 
+// a caller's model as sw_batch_oligo_hits_thermo takes it (host pointers)
+struct ThermoModel {
+    const int16_t *stack, *end;
+    const int32_t *init;
+    int32_t max_dg;                  // INT32_MAX: no threshold
+};
+
+// what a model says about itself, before a device is touched: the stable key relies on the bound of the dg plane
+void check_model(const ThermoModel &m)
+{
+    if (!m.stack || !m.end || !m.init) raise(SW_ERR_VALUE, "oligo hits: a NULL handle or array");
+    for (uint32_t i = 0; i < olt::STACK_PLANE; ++i)
+        if (std::abs((int)m.stack[olt::DG * olt::STACK_PLANE + i]) > olt::MAX_DG)
+            raise(SW_ERR_VALUE, "oligo hits: the model's dg of stack %u is %d; |dg| <= %d is taken", i, (int)m.stack[olt::DG * olt::STACK_PLANE + i], olt::MAX_DG);
+    for (uint32_t i = 0; i < olt::END_PLANE; ++i)
+        if (std::abs((int)m.end[olt::DG * olt::END_PLANE + i]) > olt::MAX_DG)
+            raise(SW_ERR_VALUE, "oligo hits: the model's dg of end %u is %d; |dg| <= %d is taken", i, (int)m.end[olt::DG * olt::END_PLANE + i], olt::MAX_DG);
+    if (m.init[olt::DG] > olt::MAX_DG || m.init[olt::DG] < -olt::MAX_DG)
+        raise(SW_ERR_VALUE, "oligo hits: the model's dg of init is %d; |dg| <= %d is taken", (int)m.init[olt::DG], olt::MAX_DG);
+}
+
+// th: the model of a call with one (section 3.2o), else nullptr -- then nothing below differs from the search without it
 void batch_oligo_hits(const sw_batch &b, const uint64_t *offsets, const char *blob, uint64_t nq, uint32_t lmin, uint32_t max_mm, uint32_t three_prime,
-                      bool want_sites, hipStream_t stream, sw_oligos &o)
+                      bool want_sites, hipStream_t stream, sw_oligos &o, const ThermoModel *th = nullptr)
 {
     const HostBatch &h = b.host;
     const uint64_t n_asm = h.n_assemblies, cells = nq * n_asm;
@@ -435,6 +558,28 @@ void batch_oligo_hits(const sw_batch &b, const uint64_t *offsets, const char *bl
         o.field[f].alloc(cells);
         if (cells) SW_HIP(hipMemsetAsync(o.field[f].p, f ? 0xFF : 0, cells * 4, stream));
     }
+    DevArray<int16_t> d_model;               // the model's stack and end tables
+    DevArray<uint32_t> all_rows;             // with the list: the pattern rows of every oligo (k_ol_thermo_sites)
+    olt::Tables model{};
+    if (th) {
+        o.thermo = true;
+        o.n_stable.alloc(cells);
+        if (cells) SW_HIP(hipMemsetAsync(o.n_stable.p, 0, cells * 4, stream));
+        for (int f = 0; f < 3; ++f) {        // (k_ol_thermo_best fills them; a batch without a run of lmin bases launches nothing)
+            o.stable_sum[f].alloc(cells);
+            if (cells) SW_HIP(hipMemsetD32Async((hipDeviceptr_t)o.stable_sum[f].p, (int)olt::NO_SUM, cells, stream));
+        }
+        for (int f = 0; f < 4; ++f) {
+            o.stable_at[f].alloc(cells);
+            if (cells) SW_HIP(hipMemsetAsync(o.stable_at[f].p, 0xFF, cells * 4, stream));
+        }
+        d_model.alloc(olt::STACK_WORDS + olt::END_WORDS);
+        SW_HIP(hipMemcpyAsync(d_model.p, th->stack, olt::STACK_WORDS * 2, hipMemcpyHostToDevice, stream));
+        SW_HIP(hipMemcpyAsync(d_model.p + olt::STACK_WORDS, th->end, olt::END_WORDS * 2, hipMemcpyHostToDevice, stream));
+        model.stack = d_model.p;
+        model.end = d_model.p + olt::STACK_WORDS;
+        for (uint32_t i = 0; i < olt::PLANES; ++i) model.init[i] = th->init[i];
+    }
     // ---- the runs of lmin bases or more: a tile's "k-mers" are window ends (kmer_walk.hpp) ----
     RunTiles T;
     build_run_tiles(h, lmin, "oligo hits", T);
@@ -447,6 +592,12 @@ void batch_oligo_hits(const sw_batch &b, const uint64_t *offsets, const char *bl
     uint64_t passes = 0, chunks = 0, launches = 0, hits = 0, grows = 0, splits = 0, windows = 0, comparisons = 0;
     std::vector<DevArray<uint64_t>> lists;   // the chunks' site keys, in the order the chunks ended
     Event e0, e1, e2;
+    std::unique_ptr<Event> ta, tb;           // the model's kernels are timed by events of their own: none without a model
+    if (th) {
+        ta.reset(new Event);
+        tb.reset(new Event);
+    }
+    double best_ms = 0;
     SW_HIP(hipEventRecord(e0, stream));
     DevRunTiles runs(T, b.d_packed.p, stream, true);
     if (T.tiles && cells) {
@@ -454,7 +605,8 @@ void batch_oligo_hits(const sw_batch &b, const uint64_t *offsets, const char *bl
         DevArray<uint32_t> tab(group * 2 * OL_ROW);
         DevArray<unsigned long long> best(group * n_asm), d_cursor(1), buf;
         if (want_sites) buf.alloc(cap);
-        ScanArgs g{};
+        DevArray<unsigned long long> stable;
+        ThermoScanArgs g{};                      // (a call without a model passes its ScanArgs part)
         g.tab = tab.p;
         g.lmin = lmin;
         g.max_mm = max_mm;
@@ -462,6 +614,15 @@ void batch_oligo_hits(const sw_batch &b, const uint64_t *offsets, const char *bl
         g.n_sites = o.field[0].p;
         g.best = best.p;
         g.cursor = d_cursor.p;
+        if (th) {
+            stable.alloc(group * n_asm);
+            g.model = model;
+            g.max_dg = th->max_dg;
+            g.n_stable = o.n_stable.p;
+            g.stable = stable.p;
+            if (want_sites) all_rows.alloc(nq * 2 * OL_ROW);
+        }
+        const StableFields sf{o.stable_sum[0].p, o.stable_sum[1].p, o.stable_sum[2].p, o.stable_at[0].p, o.stable_at[1].p, o.stable_at[2].p, o.stable_at[3].p};
         uint64_t rows = n_asm;
         for (uint64_t q0 = 0; q0 < nq; q0 += group, ++passes) {
             const uint64_t qn = std::min<uint64_t>(group, nq - q0);
@@ -469,6 +630,10 @@ void batch_oligo_hits(const sw_batch &b, const uint64_t *offsets, const char *bl
                 pattern_rows(blob + offsets[q0 + q], (uint32_t)(offsets[q0 + q + 1] - offsets[q0 + q]), three_prime, rows_host.data() + q * 2 * OL_ROW);
             SW_HIP(hipMemcpyAsync(tab.p, rows_host.data(), qn * 2 * OL_ROW * 4, hipMemcpyHostToDevice, stream));
             SW_HIP(hipMemsetAsync(best.p, 0xFF, qn * n_asm * 8, stream));
+            if (th) {
+                SW_HIP(hipMemsetAsync(stable.p, 0xFF, qn * n_asm * 8, stream));
+                if (want_sites) SW_HIP(hipMemcpyAsync(all_rows.p + q0 * 2 * OL_ROW, tab.p, qn * 2 * OL_ROW * 4, hipMemcpyDeviceToDevice, stream));
+            }
             g.n_pat = (uint32_t)(2 * qn);
             g.q0 = (uint32_t)q0;
             for (uint64_t a0 = 0; a0 < n_asm;) {
@@ -477,13 +642,17 @@ void batch_oligo_hits(const sw_batch &b, const uint64_t *offsets, const char *bl
                 g.buf = buf.p;
                 g.cap = cap;
                 g.v = runs.view(T.asm_tile_off[a0], T.asm_tile_off[a1]);
-                launches += launch_tiles(k_ol_scan, g, blocks_max, stream);
+                launches += th ? launch_tiles(k_ol_scan<true>, g, blocks_max, stream) : launch_tiles(k_ol_scan<false>, (ScanArgs)g, blocks_max, stream);
                 unsigned long long n = 0;
                 SW_HIP(hipMemcpyAsync(&n, d_cursor.p, 8, hipMemcpyDeviceToHost, stream));
                 SW_HIP(hipStreamSynchronize(stream));   // (the pattern rows of the host are free again, too)
                 if (want_sites && n > cap) {
                     // the chunk's counts are partial: its columns of this pass's rows are cleared (the best sites are minima: a redo changes nothing)
                     SW_HIP(hipMemset2DAsync(o.field[0].p + q0 * n_asm + a0, n_asm * 4, 0, (a1 - a0) * 4, qn, stream));
+                    if (th) {   // n_stable is as partial as n_sites; the stable keys go with it (minima, like the best sites: the redo finds them again)
+                        SW_HIP(hipMemset2DAsync(o.n_stable.p + q0 * n_asm + a0, n_asm * 4, 0, (a1 - a0) * 4, qn, stream));
+                        SW_HIP(hipMemset2DAsync(stable.p + a0, n_asm * 8, 0xFF, (a1 - a0) * 8, qn, stream));
+                    }
                     if (a1 - a0 > 1) {   // redone in two halves: the first now, the second is the next chunk
                         rows = (a1 - a0 + 1) / 2;
                         ++splits;
@@ -508,6 +677,15 @@ void batch_oligo_hits(const sw_batch &b, const uint64_t *offsets, const char *bl
             }
             launch_1d(k_ol_resolve, qn * n_asm, stream, (const unsigned long long *)best.p, q0 * n_asm, runs.view(), o.field[1].p, o.field[2].p, o.field[3].p,
                       o.field[4].p);
+            if (th) {
+                SW_HIP(hipEventRecord(*ta, stream));
+                launch_1d(k_ol_thermo_best, qn * n_asm, stream, (const unsigned long long *)stable.p, q0 * n_asm, runs.view(), (const uint32_t *)tab.p, n_asm, model, sf);
+                SW_HIP(hipEventRecord(*tb, stream));
+                SW_HIP(hipEventSynchronize(*tb));   // (the table is rewritten by the next pass)
+                float t = 0;
+                SW_HIP(hipEventElapsedTime(&t, *ta, *tb));
+                best_ms += t;
+            }
         }
     }
     SW_HIP(hipEventRecord(e1, stream));
@@ -532,12 +710,23 @@ void batch_oligo_hits(const sw_batch &b, const uint64_t *offsets, const char *bl
         launch_1d(k_ol_decode, hits, stream, (const uint64_t *)o.keys.p, runs.view(), o.s_asm.p, o.s_rec.p, o.s_pos.p);
     }
     SW_HIP(hipEventRecord(e2, stream));
+    if (th && want_sites && hits) {
+        for (int f = 0; f < 3; ++f) o.s_sum[f].alloc(hits);
+        launch_1d(k_ol_thermo_sites, hits, stream, (const uint64_t *)o.keys.p, b.d_packed.p, (const uint32_t *)all_rows.p, model, o.s_sum[0].p, o.s_sum[1].p,
+                  o.s_sum[2].p);
+        SW_HIP(hipEventRecord(*tb, stream));
+    }
     SW_HIP(hipStreamSynchronize(stream));   // (the temporaries go back to the pool behind the kernels)
     float ms = 0;
     SW_HIP(hipEventElapsedTime(&ms, e0, e1));
-    o.ms[0] = ms;
+    o.ms[0] = std::max(0.0, (double)ms - best_ms);
     SW_HIP(hipEventElapsedTime(&ms, e1, e2));
     o.ms[1] = ms;
+    o.thermo_ms[0] = best_ms;
+    if (th && want_sites && hits) {
+        SW_HIP(hipEventElapsedTime(&ms, e2, *tb));
+        o.thermo_ms[1] = ms;
+    }
     const uint64_t cn[8] = {windows, passes, chunks, launches, hits, grows, splits, comparisons};
     memcpy(o.counters, cn, sizeof cn);
 }
@@ -875,6 +1064,77 @@ int sw_oligos_stats(const sw_oligos *h, uint64_t *counters, double *ms)
         if (!h) raise(SW_ERR_VALUE, "oligo hits: a NULL handle");
         if (counters) memcpy(counters, h->counters, sizeof h->counters);
         if (ms) memcpy(ms, h->ms, sizeof h->ms);
+    });
+}
+
+int sw_batch_oligo_hits_thermo(const sw_batch *batch, const uint64_t *offsets, const char *blob, uint64_t n_oligos, uint64_t max_mismatch, uint64_t three_prime,
+                               int want_sites, void *stream, const int16_t *stack, const int16_t *end, const int32_t *init, int64_t max_dg, int no_threshold,
+                               sw_oligos **out)
+{
+    return guarded([&] {
+        const uint32_t lmin = check_oligos(offsets, blob, n_oligos, max_mismatch, three_prime);
+        const ThermoModel th{stack, end, init, no_threshold ? INT32_MAX : (int32_t)std::min<int64_t>(std::max<int64_t>(max_dg, INT32_MIN), INT32_MAX)};
+        check_model(th);
+        if (!batch || !out) raise(SW_ERR_VALUE, "oligo hits: a NULL handle or array");
+        require_device(batch->device, "the batch");
+        StreamScope scope((hipStream_t)stream);
+        std::unique_ptr<sw_oligos> o(new sw_oligos);
+        o->device = batch->device;
+        batch_oligo_hits(*batch, offsets, blob, n_oligos, lmin, (uint32_t)max_mismatch, (uint32_t)three_prime, want_sites != 0, (hipStream_t)stream, *o, &th);
+        *out = o.release();
+    });
+}
+
+int sw_oligos_thermo_block(const sw_oligos *h, uint64_t field, uint64_t r0, uint64_t r1, uint64_t c0, uint64_t c1, void *out)
+{
+    return guarded([&] {
+        if (!h) raise(SW_ERR_VALUE, "oligo hits: a NULL handle");
+        if (!h->thermo) raise(SW_ERR_VALUE, "oligo hits: these hits were made without a thermodynamic model");
+        if (field > 7)
+            raise(SW_ERR_VALUE, "oligo hits: thermo field %llu; 0 n_stable, 1 stable_dg, 2 stable_dh, 3 stable_ds, 4 stable_record, 5 stable_pos, 6 stable_strand, 7 stable_mm",
+                  (unsigned long long)field);
+        if (r0 > r1 || r1 > h->nq || c0 > c1 || c1 > h->n_asm)
+            raise(SW_ERR_VALUE, "oligo hits: rows [%llu, %llu) x columns [%llu, %llu) lie outside the %llu oligos x %llu assemblies", (unsigned long long)r0,
+                  (unsigned long long)r1, (unsigned long long)c0, (unsigned long long)c1, (unsigned long long)h->nq, (unsigned long long)h->n_asm);
+        const uint64_t nr = r1 - r0, nc = c1 - c0;
+        if (!nr || !nc) return;
+        if (!out) raise(SW_ERR_VALUE, "oligo hits: a NULL handle or array");
+        require_device(h->device, "the oligo hits");
+        const void *src = field == 0 ? (const void *)h->n_stable.p : field < 4 ? (const void *)h->stable_sum[field - 1].p : (const void *)h->stable_at[field - 4].p;
+        SW_HIP(hipMemcpy2D(out, nc * 4, (const char *)src + (r0 * h->n_asm + c0) * 4, h->n_asm * 4, nc * 4, nr, hipMemcpyDeviceToHost));
+    });
+}
+
+int sw_oligos_sites_thermo(const sw_oligos *h, int32_t *dh, int32_t *ds, int32_t *dg)
+{
+    return guarded([&] {
+        if (!h) raise(SW_ERR_VALUE, "oligo hits: a NULL handle");
+        if (!h->thermo) raise(SW_ERR_VALUE, "oligo hits: these hits were made without a thermodynamic model");
+        if (!h->has_sites) raise(SW_ERR_VALUE, "oligo hits: these hits were made without the site list");
+        if (!h->n_list) return;
+        if (!dh || !ds || !dg) raise(SW_ERR_VALUE, "oligo hits: a NULL handle or array");
+        require_device(h->device, "the oligo hits");
+        int32_t *dst[3] = {dh, ds, dg};
+        for (int f = 0; f < 3; ++f) SW_HIP(hipMemcpy(dst[f], h->s_sum[f].p, h->n_list * 4, hipMemcpyDeviceToHost));
+    });
+}
+
+int sw_oligos_thermo_stats(const sw_oligos *h, uint64_t *stable_hits, double *ms)
+{
+    return guarded([&] {
+        if (!h) raise(SW_ERR_VALUE, "oligo hits: a NULL handle");
+        if (!h->thermo) raise(SW_ERR_VALUE, "oligo hits: these hits were made without a thermodynamic model");
+        if (stable_hits) {   // summed when asked for: the search itself never reads n_stable back
+            const uint64_t cells = h->nq * h->n_asm;
+            std::vector<uint32_t> n(cells);
+            if (cells) {
+                require_device(h->device, "the oligo hits");
+                SW_HIP(hipMemcpy(n.data(), h->n_stable.p, cells * 4, hipMemcpyDeviceToHost));
+            }
+            *stable_hits = 0;
+            for (uint32_t x : n) *stable_hits += x;
+        }
+        if (ms) memcpy(ms, h->thermo_ms, sizeof h->thermo_ms);
     });
 }
 

@@ -340,15 +340,23 @@ class Batch:
         check(fn(self._h, _ptr(offs), blob, c_u64(nq), c_u64(int(kmerlen)), ctypes.byref(h)))
         return BestHits(h, aligned=bool(align))
 
-    def oligo_hits(self, oligos, max_mismatch: int = 0, three_prime: int = 0, sites: bool = False, stream: int = 0, max_edits=None) -> "OligoHits":
+    def oligo_hits(self, oligos, max_mismatch: int = 0, three_prime: int = 0, sites: bool = False, stream: int = 0, max_edits=None, thermo=None,
+                   max_dg=None) -> "OligoHits":
         """Every place in every assembly where an oligo (a list of ``str`` or ``bytes``: primers, probes) binds with at most
         ``max_mismatch`` mismatches, on either strand -- exhaustively, every window of the batch against every oligo, no seed
         (csrc/oligo.hip).  An oligo is 8..32 letters in either case: ``ACGT``, ``U`` (= T) or an IUPAC code
         ``RYSWKMBDHVN``; every position is a set of bases.  Strand 0 is the oligo, strand 1 its reverse complement.  A site is a window
         inside one valid run of a record, ``mm`` the number of its bases outside the set they face; a hit has ``mm <= max_mismatch``
         (0..8, below the shortest oligo) and no mismatch among the ``three_prime`` (0..8) bases at the oligo's 3' end.  An oligo that
-        equals its reverse complement hits twice at one place.  ``sites=True`` also keeps the list of all hits.  Not BLAST and not a
-        thermodynamic model: no Tm, no dG, no e-values.  ValueError for anything else, before a device is touched.
+        equals its reverse complement hits twice at one place.  ``sites=True`` also keeps the list of all hits.  Not BLAST: no
+        e-values.  ValueError for anything else, before a device is touched.
+
+        ``thermo`` (a :class:`seqwin_amd.oligos.ThermoModel`, e.g. ``oligos.santalucia98()``) also sums the
+        model's integer tables over every hit: ``dh``, ``ds``, ``dg`` of the duplex the oligo forms there.  Per (oligo, assembly)
+        ``n_stable`` counts the hits with ``dg <= max_dg`` (cal/mol; ``None``: every hit) and the ``stable_*`` fields describe the
+        hit that is least in (dg, record, pos, strand) among ALL hits; with ``sites=True`` every entry of the list gets ``dh``,
+        ``ds``, ``dg``.  The hits themselves are those of the call without it.  Not together with ``max_edits`` (ValueError): a
+        bulge needs loop parameters.  No Tm on the device: :func:`seqwin_amd.oligos.melting_temperature`.
 
         ``max_edits`` (0..4, ``max_edits + three_prime`` below the shortest oligo, ``max_mismatch`` left at 0) searches by unit-cost
         edit distance instead, so that a site with a bulge of a base or two is found: an end ``e`` of a
@@ -361,6 +369,24 @@ class Batch:
         offs = np.zeros(len(qs) + 1, np.uint64)
         np.cumsum([len(q) for q in qs], out=offs[1:])
         h = c_vp()
+        if thermo is not None or max_dg is not None:
+            from .oligos import ThermoModel
+            if max_edits is not None:
+                raise ValueError("thermo and max_edits exclude each other: a site with a bulge needs loop parameters")
+            if not isinstance(thermo, ThermoModel):
+                raise ValueError("thermo must be a seqwin_amd.oligos.ThermoModel (max_dg needs one)")
+            if max_dg is not None:
+                try:
+                    whole = int(max_dg) == max_dg and -2 ** 31 <= int(max_dg) < 2 ** 31
+                except (TypeError, ValueError, OverflowError):
+                    whole = False
+                if not whole:
+                    raise ValueError(f"max_dg must be an integer of cal/mol that fits int32 (got {max_dg!r})")
+            check(lib.sw_batch_oligo_hits_thermo(self._h, _ptr(offs), b"".join(qs), c_u64(len(qs)), c_u64(int(max_mismatch)), c_u64(int(three_prime)),
+                                                 ctypes.c_int(1 if sites else 0), c_vp(stream), _ptr(thermo.stack), _ptr(thermo.end), _ptr(thermo.init),
+                                                 ctypes.c_int64(0 if max_dg is None else int(max_dg)), ctypes.c_int(1 if max_dg is None else 0),
+                                                 ctypes.byref(h)))
+            return OligoHits(h, [len(q) for q in qs], bool(sites), thermo=True)
         if max_edits is None:
             check(lib.sw_batch_oligo_hits(self._h, _ptr(offs), b"".join(qs), c_u64(len(qs)), c_u64(int(max_mismatch)), c_u64(int(three_prime)),
                                           ctypes.c_int(1 if sites else 0), c_vp(stream), ctypes.byref(h)))
@@ -1180,7 +1206,8 @@ class OligoHits:
     """The sites of a list of oligos in every assembly of a batch, resident on the device (:meth:`Batch.oligo_hits`; csrc/oligo.hip,
     DESIGN.md section 3.2j): per (oligo, assembly) ``n_sites``, the number of hits on both strands, and the hit that is least in the
     order (mm, record, pos, strand) as ``best_mm``, ``best_record`` (global), ``best_pos`` and ``best_strand`` -- NO_HIT without a
-    hit.  It has no counterpart in the reference, is not BLAST, is no thermodynamic model and fills none of ``MarkerMetrics``.  A
+    hit.  It has no counterpart in the reference, is not BLAST and fills none of ``MarkerMetrics``.  Made with ``thermo=`` (DESIGN.md
+    section 3.2o) it also holds ``n_stable`` and the ``stable_*`` fields of the hit that is least in (dg, record, pos, strand).  A
     single-device object on a resident batch.  ``rows`` (oligos) / ``cols`` (assemblies) are None (all), a ``(lo, hi)`` pair, a slice
     or a range.  Made with ``sites=True`` it also holds the list of all hits.
 
@@ -1188,10 +1215,11 @@ class OligoHits:
     site is the least in (dist, record, pos, strand), then end, and ``best_mm`` is a ValueError: ask for ``best_dist``.  On a result
     without it ``dist`` and ``mismatch`` are ``mm``, ``end`` is ``pos + L`` and ``gaps`` is 0."""
 
-    def __init__(self, handle: c_vp, lengths, sites: bool = False):
+    def __init__(self, handle: c_vp, lengths, sites: bool = False, thermo: bool = False):
         self._h = handle
         self.lengths = np.asarray(lengths, np.uint32)
         self._sites = sites
+        self.thermo = thermo
         v = ctypes.c_int64()
         check(lib.sw_oligos_max_edits(self._h, ctypes.byref(v)))
         self.max_edits = None if v.value < 0 else int(v.value)
@@ -1240,6 +1268,45 @@ class OligoHits:
     def best_strand(self, rows=None, cols=None) -> np.ndarray:
         return self._block(4, rows, cols)
 
+    def _thermo_block(self, field: int, rows, cols, dtype) -> np.ndarray:
+        if not self.thermo:
+            raise ValueError("these oligo hits were made without thermo=")
+        nq, na, _, _ = self.sizes()
+        (r0, r1), (c0, c1) = _block_range(rows, nq), _block_range(cols, na)
+        out = np.empty((max(r1 - r0, 0), max(c1 - c0, 0)), dtype)
+        check(lib.sw_oligos_thermo_block(self._h, c_u64(field), c_u64(r0), c_u64(r1), c_u64(c0), c_u64(c1), _ptr(out)))
+        return out
+
+    def n_stable(self, rows=None, cols=None) -> np.ndarray:
+        """uint32[rows, cols]: the hits with ``dg <= max_dg`` (every hit without a ``max_dg``).  This and the ``stable_*`` fields:
+        ValueError on a result made without ``thermo=``."""
+        return self._thermo_block(0, rows, cols, np.uint32)
+
+    def stable_dg(self, rows=None, cols=None) -> np.ndarray:
+        """int32[rows, cols], cal/mol: dg of the most stable hit -- the least in (dg, record, pos, strand) among all hits, stable or
+        not; INT32_MIN (``oligos.NO_SUM``) without a hit, as ``stable_dh`` and ``stable_ds``."""
+        return self._thermo_block(1, rows, cols, np.int32)
+
+    def stable_dh(self, rows=None, cols=None) -> np.ndarray:
+        return self._thermo_block(2, rows, cols, np.int32)
+
+    def stable_ds(self, rows=None, cols=None) -> np.ndarray:
+        return self._thermo_block(3, rows, cols, np.int32)
+
+    def stable_record(self, rows=None, cols=None) -> np.ndarray:
+        """uint32[rows, cols]: the most stable hit's record (global); NO_HIT without a hit, as ``stable_pos``, ``stable_strand`` and
+        ``stable_mm``."""
+        return self._thermo_block(4, rows, cols, np.uint32)
+
+    def stable_pos(self, rows=None, cols=None) -> np.ndarray:
+        return self._thermo_block(5, rows, cols, np.uint32)
+
+    def stable_strand(self, rows=None, cols=None) -> np.ndarray:
+        return self._thermo_block(6, rows, cols, np.uint32)
+
+    def stable_mm(self, rows=None, cols=None) -> np.ndarray:
+        return self._thermo_block(7, rows, cols, np.uint32)
+
     def sites(self) -> dict:
         """Every hit, ascending by (oligo, assembly, record, pos, strand), as parallel uint32 arrays ``oligo``, ``assembly``,
         ``record``, ``pos``, ``strand``, ``end``, ``dist``, ``mismatch``, ``gaps`` -- and ``mm`` on a result without ``max_edits``;
@@ -1256,6 +1323,10 @@ class OligoHits:
             check(lib.sw_oligos_sites(self._h, _ptr(offs), *[_ptr(a) if n.value else None for a in cols]))
             out = dict(zip(SITE_FIELDS, cols))
             out.update(end=out["pos"] + self.lengths[out["oligo"]], dist=out["mm"].copy(), mismatch=out["mm"].copy(), gaps=np.zeros(n.value, np.uint32))
+            if self.thermo:                # int32 dh, ds, dg of every entry (section 3.2o)
+                sums = [np.empty(n.value, np.int32) for _ in range(3)]
+                check(lib.sw_oligos_sites_thermo(self._h, *[_ptr(a) if n.value else None for a in sums]))
+                out.update(dh=sums[0], ds=sums[1], dg=sums[2])
         else:
             cols = [np.empty(n.value, np.uint32) for _ in SITE_FIELDS_EDIT]
             check(lib.sw_oligos_sites_edit(self._h, _ptr(offs), *[_ptr(a) if n.value else None for a in cols]))
@@ -1276,7 +1347,9 @@ class OligoHits:
         """``windows`` (window ends scanned, summed over the passes), ``passes`` (groups of oligos), ``chunks`` (of assemblies),
         ``launches``, ``hits``, ``buffer_doublings``, ``chunk_splits``, ``comparisons`` (window x oligo x strand), ``scan_ms`` and
         ``order_ms`` (HIP events); ``dp_steps`` (steps of the bit-vector column, an upper bound), ``candidates`` (resolved by the
-        alignment kernel) and ``resolve_ms`` -- zeros without ``max_edits``; with it ``scan_ms`` excludes ``resolve_ms``."""
+        alignment kernel) and ``resolve_ms`` -- zeros without ``max_edits``; with it ``scan_ms`` excludes ``resolve_ms``.
+        ``stable_hits`` (the sum of ``n_stable``), ``thermo_ms`` (the kernel of the ``stable_*`` fields; ``scan_ms`` excludes it)
+        and ``site_thermo_ms`` (the kernel of the list's sums) -- zeros without ``thermo=``."""
         c = (c_u64 * 8)()
         ms = (ctypes.c_double * 2)()
         check(lib.sw_oligos_stats(self._h, c, ms))
@@ -1286,6 +1359,12 @@ class OligoHits:
         ms2 = ctypes.c_double()
         check(lib.sw_oligos_edit_stats(self._h, c2, ctypes.byref(ms2)))
         d.update(dp_steps=int(c2[0]), candidates=int(c2[1]), resolve_ms=ms2.value)
+        d.update(stable_hits=0, thermo_ms=0.0, site_thermo_ms=0.0)   # (zeros without thermo=)
+        if self.thermo:
+            n3 = c_u64()
+            ms3 = (ctypes.c_double * 2)()
+            check(lib.sw_oligos_thermo_stats(self._h, ctypes.byref(n3), ms3))
+            d.update(stable_hits=int(n3.value), thermo_ms=ms3[0], site_thermo_ms=ms3[1])
         return d
 
     def close(self) -> None:
