@@ -1212,14 +1212,7 @@ int sw_hits_align_block(const sw_hits *h, uint64_t field, uint64_t r0, uint64_t 
         if (!h) raise(SW_ERR_VALUE, "best hits: a NULL handle");
         if (!h->aligned) raise(SW_ERR_VALUE, "best hits: these hits were made without the alignment (sw_batch_best_hits_aligned makes it)");
         if (field > 3) raise(SW_ERR_VALUE, "best hits: field %llu is none of a_start, nident, mismatch, gaps (0..3)", (unsigned long long)field);
-        if (r0 > r1 || r1 > h->nq || c0 > c1 || c1 > h->n_asm)
-            raise(SW_ERR_VALUE, "best hits: rows [%llu, %llu) x columns [%llu, %llu) lie outside the %llu queries x %llu assemblies", (unsigned long long)r0,
-                  (unsigned long long)r1, (unsigned long long)c0, (unsigned long long)c1, (unsigned long long)h->nq, (unsigned long long)h->n_asm);
-        const uint64_t nr = r1 - r0, nc = c1 - c0;
-        if (!nr || !nc) return;
-        if (!out) raise(SW_ERR_VALUE, "best hits: a NULL handle or array");
-        require_device(h->device, "the hits");
-        SW_HIP(hipMemcpy2D(out, nc * 4, h->afield[field].p + r0 * h->n_asm + c0, h->n_asm * 4, nc * 4, nr, hipMemcpyDeviceToHost));
+        export_cells("best hits", "queries", h->device, "the hits", h->afield[field].p, h->nq, h->n_asm, r0, r1, c0, c1, out);
     });
 }
 

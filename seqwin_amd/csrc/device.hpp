@@ -38,6 +38,22 @@ inline void require_device(int device, const char *what)
         raise(SW_ERR_VALUE, "%s lives on device %d but the calling thread's current device is %d (sw_set_device)", what, device, cur);
 }
 
+// rows [r0, r1) x columns [c0, c1) of a [n_rows][n_cols] device table of 32-bit cells -> out, row-major: what every block export of
+// the query layer ends with.  what: the prefix of the messages ("best hits"), rows_name: the noun of the rows ("queries"), device and
+// device_name: require_device's.  An empty block is a valid call that touches neither `out` nor the device.
+inline void export_cells(const char *what, const char *rows_name, int device, const char *device_name, const void *table, uint64_t n_rows, uint64_t n_cols,
+                         uint64_t r0, uint64_t r1, uint64_t c0, uint64_t c1, void *out)
+{
+    if (r0 > r1 || r1 > n_rows || c0 > c1 || c1 > n_cols)
+        raise(SW_ERR_VALUE, "%s: rows [%llu, %llu) x columns [%llu, %llu) lie outside the %llu %s x %llu assemblies", what, (unsigned long long)r0,
+              (unsigned long long)r1, (unsigned long long)c0, (unsigned long long)c1, (unsigned long long)n_rows, rows_name, (unsigned long long)n_cols);
+    const uint64_t nr = r1 - r0, nc = c1 - c0;
+    if (!nr || !nc) return;
+    if (!out) raise(SW_ERR_VALUE, "%s: a NULL handle or array", what);
+    require_device(device, device_name);
+    SW_HIP(hipMemcpy2D(out, nc * 4, (const char *)table + (r0 * n_cols + c0) * 4, n_cols * 4, nc * 4, nr, hipMemcpyDeviceToHost));
+}
+
 constexpr uint32_t MAX_LAUNCH_BLOCKS = 1u << 22;   // workgroups per launch: 2^30 threads of 256, below the 2^32 a launch may hold
 
 // workgroups per launch; the switch named env_name (test library) lowers it, so that a small input needs several launches -- what

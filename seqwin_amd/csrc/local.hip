@@ -460,14 +460,7 @@ int sw_hits_local_block(const sw_hits *h, uint64_t field, uint64_t r0, uint64_t 
         local_of(h);
         if (field >= LOCAL_FIELDS)
             raise(SW_ERR_VALUE, "best hits: field %llu is none of score, qstart, qend, sstart, send, nident, mismatch, gapopen, gaps (0..8)", (unsigned long long)field);
-        if (r0 > r1 || r1 > h->nq || c0 > c1 || c1 > h->n_asm)
-            raise(SW_ERR_VALUE, "best hits: rows [%llu, %llu) x columns [%llu, %llu) lie outside the %llu queries x %llu assemblies", (unsigned long long)r0,
-                  (unsigned long long)r1, (unsigned long long)c0, (unsigned long long)c1, (unsigned long long)h->nq, (unsigned long long)h->n_asm);
-        const uint64_t nr = r1 - r0, nc = c1 - c0;
-        if (!nr || !nc) return;
-        if (!out) raise(SW_ERR_VALUE, "best hits: a NULL handle or array");
-        require_device(h->device, "the hits");
-        SW_HIP(hipMemcpy2D(out, nc * 4, h->lfield[field].p + r0 * h->n_asm + c0, h->n_asm * 4, nc * 4, nr, hipMemcpyDeviceToHost));
+        export_cells("best hits", "queries", h->device, "the hits", h->lfield[field].p, h->nq, h->n_asm, r0, r1, c0, c1, out);
     });
 }
 

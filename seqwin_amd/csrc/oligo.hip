@@ -19,7 +19,7 @@
 //                  a site iff e + 1 >= L --, counts it (atomicAdd), offers it as the best site (64-bit atomicMin) and appends it to
 //                  the site buffer (wave_append).  All three are order-independent.
 //   k_ol_resolve   the best site's key -> mm, record, pos, strand of a cell
-//   k_ol_decode    a sorted site key -> assembly, record, pos
+//   k_ol_decode    a sorted site key -> assembly, record, pos (a template over where the key keeps the base index: both routes)
 // With a thermodynamic model (tests/tools/oligo_thermo_host.py; oligo_thermo_core.hpp holds the site sum):
 //   k_ol_scan<true>     the same walk; behind the candidate ballot, where mm is recomputed per hit anyway, it also sums the site's
 //                       dg, counts it where dg <= max_dg (atomicAdd) and offers it as the most stable site (a second 64-bit
@@ -40,7 +40,7 @@
 //                  (oligo, strand, a base of the run that names the end).
 //   k_ole_resolve  a thread per candidate: the small matrix and the canonical traceback give pos, end, mismatch and gaps; the site is
 //                  counted, offered as the cell's best (64-bit atomicMin) and its buffer entry becomes the sortable site key
-//   k_ole_best     the best site's key -> the seven best fields of a cell;  k_ole_decode  a sorted site key -> assembly, record, pos
+//   k_ole_best     the best site's key -> the seven best fields of a cell;  k_ol_decode with this route's shift: the list's columns
 #include "screen_core.hpp"
 #include "oligo_edit_core.hpp"
 #include "oligo_thermo_core.hpp"
@@ -228,12 +228,14 @@ __global__ __launch_bounds__(SCR_TPB) void k_ol_resolve(uint64_t base, uint64_t 
     strand[cell0 + i] = (uint32_t)(key & 1);
 }
 
+// sorted site key i of either route -> assembly, record, pos; the key holds the base index in its bits [IDX_SHIFT, IDX_SHIFT + IDX_BITS)
+template <uint32_t IDX_SHIFT, uint32_t IDX_BITS>
 __global__ __launch_bounds__(SCR_TPB) void k_ol_decode(uint64_t base, uint64_t end, const uint64_t *__restrict__ keys, RunView v, uint32_t *__restrict__ asm_out,
                                                        uint32_t *__restrict__ rec, uint32_t *__restrict__ pos)
 {
     const uint64_t i = base + (uint64_t)blockIdx.x * SCR_TPB + threadIdx.x;
     if (i >= end) return;
-    const uint64_t idx = (keys[i] & ((1ull << OL_SITE_Q_SHIFT) - 1)) >> OL_SITE_IDX_SHIFT;
+    const uint64_t idx = (keys[i] >> IDX_SHIFT) & ((1ull << IDX_BITS) - 1);
     const uint32_t r = ol_run_of(v.run_base, v.n_runs, idx);
     asm_out[i] = v.run_asm[r];
     rec[i] = v.run_rec[r];
@@ -405,18 +407,6 @@ __global__ __launch_bounds__(SCR_TPB) void k_ole_best(uint64_t base, uint64_t en
     f.gaps[cell0 + i] = (over > d ? over - d : d - over) + 2 * (code / 5);
 }
 
-__global__ __launch_bounds__(SCR_TPB) void k_ole_decode(uint64_t base, uint64_t end, const uint64_t *__restrict__ keys, RunView v, uint32_t *__restrict__ asm_out,
-                                                        uint32_t *__restrict__ rec, uint32_t *__restrict__ pos)
-{
-    const uint64_t i = base + (uint64_t)blockIdx.x * SCR_TPB + threadIdx.x;
-    if (i >= end) return;
-    const uint64_t idx = (keys[i] >> OLE_IDX_SHIFT) & OLE_IDX_MASK;
-    const uint32_t r = ol_run_of(v.run_base, v.n_runs, idx);
-    asm_out[i] = v.run_asm[r];
-    rec[i] = v.run_rec[r];
-    pos[i] = v.run_pos[r] + (uint32_t)(idx - v.run_base[r]);
-}
-
 // ---- host: the oligos -------------------------------------------------------------------------------------------------------------
 // the set of bases a letter stands for (bit b: base b of A C G T), 0: no letter of an oligo
 uint32_t iupac_set(unsigned char c)
@@ -540,24 +530,120 @@ void check_model(const ThermoModel &m)
         raise(SW_ERR_VALUE, "oligo hits: the model's dg of init is %d; |dg| <= %d is taken", (int)m.init[olt::DG], olt::MAX_DG);
 }
 
+// ---- the steps batch_oligo_hits and batch_oligo_edit share, each written once ------------------------------------------------------
+struct OligoCounts {   // sw_oligos_stats, in its order
+    uint64_t windows = 0, passes = 0, chunks = 0, launches = 0, hits = 0, grows = 0, splits = 0, comparisons = 0;
+};
+static_assert(sizeof(OligoCounts) == sizeof(sw_oligos::counters), "OligoCounts is copied into sw_oligos::counters");
+
+// the start of a result: what the batch must be, the sizes, the oligos' lengths and the first n_fields cell fields (n_sites 0, the rest 0xFF)
+void start_result(const sw_batch &b, const uint64_t *offsets, uint64_t nq, uint64_t max_mm, int64_t max_edits, uint32_t three_prime, bool want_sites, int n_fields,
+                  hipStream_t stream, sw_oligos &o)
+{
+    const HostBatch &h = b.host;
+    const uint64_t cells = nq * h.n_assemblies;
+    if (h.rec_len.size() && !b.d_packed.p) raise(SW_ERR_VALUE, "oligo hits: the batch holds no packed bases (it must be resident)");
+    if ((uint64_t)h.packed_words32() * 16 >= OL_MAX_BASES) raise(SW_ERR_RUNTIME, "oligo hits: the batch has 2^43 bases or more");
+    o.nq = nq;
+    o.n_asm = h.n_assemblies;
+    o.max_mm = max_mm;
+    o.max_edits = max_edits;               // (-1: a Hamming result)
+    o.three_prime = three_prime;
+    o.has_sites = want_sites;
+    for (uint64_t q = 0; q < nq; ++q) o.lens.push_back((uint32_t)(offsets[q + 1] - offsets[q]));
+    for (int f = 0; f < n_fields; ++f) {
+        o.field[f].alloc(cells);
+        if (cells) SW_HIP(hipMemsetAsync(o.field[f].p, f ? 0xFF : 0, cells * 4, stream));
+    }
+}
+
+// how a call is cut: oligos per pass, entries of the buffer a chunk of assemblies may fill, workgroups per launch of the scan kernel;
+// the three switches (test library) lower them
+struct ChunkSizes {
+    uint64_t group, cap;
+    uint32_t blocks_max;
+};
+
+ChunkSizes chunk_sizes(uint64_t nq)
+{
+    uint64_t group = OL_GROUP, budget = OL_BUFFER_BYTES;
+    if (const char *e = SW_TEST_GETENV("SEQWIN_AMD_OLIGO_GROUP")) group = std::min<uint64_t>(std::max<uint64_t>(env_u64(e, group), 1), OL_GROUP);
+    if (const char *e = SW_TEST_GETENV("SEQWIN_AMD_OLIGO_BUFFER_KB")) budget = env_u64(e, budget >> 10) << 10;
+    return {std::min<uint64_t>(group, nq), std::min<uint64_t>(std::max<uint64_t>(budget / 8, 1), OL_MAX_SITES), launch_blocks("SEQWIN_AMD_OLIGO_MAX_BLOCKS")};
+}
+
+// the chunk of assemblies [a0, a1) overflowed the buffer and is redone: in two halves (the first now, the second is the next chunk), or,
+// one assembly above the budget, with the buffer doubled
+void overflow_step(uint64_t a0, uint64_t a1, uint64_t &rows, uint64_t &cap, DevArray<unsigned long long> &buf, OligoCounts &c)
+{
+    if (a1 - a0 > 1) {
+        rows = (a1 - a0 + 1) / 2;
+        ++c.splits;
+    } else {
+        if (cap >= OL_MAX_SITES) raise(SW_ERR_RUNTIME, "oligo hits: assembly %llu alone has 2^32 sites or more", (unsigned long long)a0);
+        cap = std::min<uint64_t>(cap * 2, OL_MAX_SITES);
+        buf.alloc(cap);
+        ++c.grows;
+    }
+}
+
+typedef void (*DecodeKernel)(uint64_t, uint64_t, const uint64_t *, RunView, uint32_t *, uint32_t *, uint32_t *);   // an instantiation of k_ol_decode
+
+// the site list: all chunks' keys in one ascending order -- (oligo, assembly, record, pos, strand), an edit result: (.., pos, end, strand)
+// -- and the three columns the keys do not hold, by the route's instantiation of the decode kernel
+void finish_site_list(std::vector<DevArray<uint64_t>> &lists, uint64_t hits, DecodeKernel decode, const RunView &v, hipStream_t stream, sw_oligos &o)
+{
+    DevArray<uint64_t> ka(hits), kb(hits);
+    uint64_t at = 0;
+    for (DevArray<uint64_t> &l : lists) {
+        SW_HIP(hipMemcpyAsync(ka.p + at, l.p, l.n * 8, hipMemcpyDeviceToDevice, stream));
+        at += l.n;
+    }
+    if (at != hits) raise(SW_ERR_RUNTIME, "internal error: the chunks' site lists do not add up");
+    uint64_t *kp = ka.p, *ap = kb.p;
+    sort_all_bits(kp, ap, hits, stream);
+    lists.clear();
+    if (kp != ka.p) std::swap(ka, kb);
+    o.keys = std::move(ka);
+    o.n_list = hits;
+    o.s_asm.alloc(hits);
+    o.s_rec.alloc(hits);
+    o.s_pos.alloc(hits);
+    launch_1d(decode, hits, stream, (const uint64_t *)o.keys.p, v, o.s_asm.p, o.s_rec.p, o.s_pos.p);
+}
+
+// the end of either route: the stream's last synchronisation, scan_ms -- e0 to e1 without what the route timed by events of its own
+// (apart_ms) --, order_ms and the counters
+void close_result(hipStream_t stream, const Event &e0, const Event &e1, const Event &e2, double apart_ms, const OligoCounts &c, sw_oligos &o)
+{
+    SW_HIP(hipStreamSynchronize(stream));   // (the temporaries go back to the pool behind the kernels)
+    float ms = 0;
+    SW_HIP(hipEventElapsedTime(&ms, e0, e1));
+    o.ms[0] = std::max(0.0, (double)ms - apart_ms);
+    SW_HIP(hipEventElapsedTime(&ms, e1, e2));
+    o.ms[1] = ms;
+    memcpy(o.counters, &c, sizeof c);
+}
+
+// what the creating entry points do behind their argument checks: search(o) fills a fresh result on the batch's device, inside the stream's scope
+template <class F> void make_oligos(const sw_batch *batch, void *stream, sw_oligos **out, F &&search)
+{
+    if (!batch || !out) raise(SW_ERR_VALUE, "oligo hits: a NULL handle or array");
+    require_device(batch->device, "the batch");
+    StreamScope scope((hipStream_t)stream);
+    std::unique_ptr<sw_oligos> o(new sw_oligos);
+    o->device = batch->device;
+    search(*o);
+    *out = o.release();
+}
+
 // th: the model of a call with one (section 3.2o), else nullptr -- then nothing below differs from the search without it
 void batch_oligo_hits(const sw_batch &b, const uint64_t *offsets, const char *blob, uint64_t nq, uint32_t lmin, uint32_t max_mm, uint32_t three_prime,
                       bool want_sites, hipStream_t stream, sw_oligos &o, const ThermoModel *th = nullptr)
 {
     const HostBatch &h = b.host;
     const uint64_t n_asm = h.n_assemblies, cells = nq * n_asm;
-    if (h.rec_len.size() && !b.d_packed.p) raise(SW_ERR_VALUE, "oligo hits: the batch holds no packed bases (it must be resident)");
-    if ((uint64_t)h.packed_words32() * 16 >= OL_MAX_BASES) raise(SW_ERR_RUNTIME, "oligo hits: the batch has 2^43 bases or more");
-    o.nq = nq;
-    o.n_asm = n_asm;
-    o.max_mm = max_mm;
-    o.three_prime = three_prime;
-    o.has_sites = want_sites;
-    for (uint64_t q = 0; q < nq; ++q) o.lens.push_back((uint32_t)(offsets[q + 1] - offsets[q]));
-    for (int f = 0; f < 5; ++f) {
-        o.field[f].alloc(cells);
-        if (cells) SW_HIP(hipMemsetAsync(o.field[f].p, f ? 0xFF : 0, cells * 4, stream));
-    }
+    start_result(b, offsets, nq, max_mm, -1, three_prime, want_sites, 5, stream, o);
     DevArray<int16_t> d_model;               // the model's stack and end tables
     DevArray<uint32_t> all_rows;             // with the list: the pattern rows of every oligo (k_ol_thermo_sites)
     olt::Tables model{};
@@ -583,13 +669,8 @@ void batch_oligo_hits(const sw_batch &b, const uint64_t *offsets, const char *bl
     // ---- the runs of lmin bases or more: a tile's "k-mers" are window ends (kmer_walk.hpp) ----
     RunTiles T;
     build_run_tiles(h, lmin, "oligo hits", T);
-    uint64_t group = OL_GROUP, budget = OL_BUFFER_BYTES;
-    if (const char *e = SW_TEST_GETENV("SEQWIN_AMD_OLIGO_GROUP")) group = std::min<uint64_t>(std::max<uint64_t>(env_u64(e, group), 1), OL_GROUP);
-    if (const char *e = SW_TEST_GETENV("SEQWIN_AMD_OLIGO_BUFFER_KB")) budget = env_u64(e, budget >> 10) << 10;
-    group = std::min<uint64_t>(group, nq);
-    uint64_t cap = std::min<uint64_t>(std::max<uint64_t>(budget / 8, 1), OL_MAX_SITES);
-    const uint32_t blocks_max = launch_blocks("SEQWIN_AMD_OLIGO_MAX_BLOCKS");   // the scan kernel's; the switch (test library) lowers it
-    uint64_t passes = 0, chunks = 0, launches = 0, hits = 0, grows = 0, splits = 0, windows = 0, comparisons = 0;
+    auto [group, cap, blocks_max] = chunk_sizes(nq);   // (cap doubles with the buffer)
+    OligoCounts cnt;
     std::vector<DevArray<uint64_t>> lists;   // the chunks' site keys, in the order the chunks ended
     Event e0, e1, e2;
     std::unique_ptr<Event> ta, tb;           // the model's kernels are timed by events of their own: none without a model
@@ -624,7 +705,7 @@ void batch_oligo_hits(const sw_batch &b, const uint64_t *offsets, const char *bl
         }
         const StableFields sf{o.stable_sum[0].p, o.stable_sum[1].p, o.stable_sum[2].p, o.stable_at[0].p, o.stable_at[1].p, o.stable_at[2].p, o.stable_at[3].p};
         uint64_t rows = n_asm;
-        for (uint64_t q0 = 0; q0 < nq; q0 += group, ++passes) {
+        for (uint64_t q0 = 0; q0 < nq; q0 += group, ++cnt.passes) {
             const uint64_t qn = std::min<uint64_t>(group, nq - q0);
             for (uint64_t q = 0; q < qn; ++q)
                 pattern_rows(blob + offsets[q0 + q], (uint32_t)(offsets[q0 + q + 1] - offsets[q0 + q]), three_prime, rows_host.data() + q * 2 * OL_ROW);
@@ -642,7 +723,7 @@ void batch_oligo_hits(const sw_batch &b, const uint64_t *offsets, const char *bl
                 g.buf = buf.p;
                 g.cap = cap;
                 g.v = runs.view(T.asm_tile_off[a0], T.asm_tile_off[a1]);
-                launches += th ? launch_tiles(k_ol_scan<true>, g, blocks_max, stream) : launch_tiles(k_ol_scan<false>, (ScanArgs)g, blocks_max, stream);
+                cnt.launches += th ? launch_tiles(k_ol_scan<true>, g, blocks_max, stream) : launch_tiles(k_ol_scan<false>, (ScanArgs)g, blocks_max, stream);
                 unsigned long long n = 0;
                 SW_HIP(hipMemcpyAsync(&n, d_cursor.p, 8, hipMemcpyDeviceToHost, stream));
                 SW_HIP(hipStreamSynchronize(stream));   // (the pattern rows of the host are free again, too)
@@ -653,23 +734,15 @@ void batch_oligo_hits(const sw_batch &b, const uint64_t *offsets, const char *bl
                         SW_HIP(hipMemset2DAsync(o.n_stable.p + q0 * n_asm + a0, n_asm * 4, 0, (a1 - a0) * 4, qn, stream));
                         SW_HIP(hipMemset2DAsync(stable.p + a0, n_asm * 8, 0xFF, (a1 - a0) * 8, qn, stream));
                     }
-                    if (a1 - a0 > 1) {   // redone in two halves: the first now, the second is the next chunk
-                        rows = (a1 - a0 + 1) / 2;
-                        ++splits;
-                    } else {             // one assembly above the budget: the buffer doubles
-                        if (cap >= OL_MAX_SITES) raise(SW_ERR_RUNTIME, "oligo hits: assembly %llu alone has 2^32 sites or more", (unsigned long long)a0);
-                        cap = std::min<uint64_t>(cap * 2, OL_MAX_SITES);
-                        buf.alloc(cap);
-                        ++grows;
-                    }
+                    overflow_step(a0, a1, rows, cap, buf, cnt);
                     continue;
                 }
-                hits += n;
-                windows += T.asm_kmers[a1] - T.asm_kmers[a0];
-                comparisons += (T.asm_kmers[a1] - T.asm_kmers[a0]) * 2 * qn;
-                ++chunks;
+                cnt.hits += n;
+                cnt.windows += T.asm_kmers[a1] - T.asm_kmers[a0];
+                cnt.comparisons += (T.asm_kmers[a1] - T.asm_kmers[a0]) * 2 * qn;
+                ++cnt.chunks;
                 if (want_sites && n) {
-                    if (hits >= OL_MAX_SITES) raise(SW_ERR_RUNTIME, "oligo hits: a site list of 2^32 entries or more");
+                    if (cnt.hits >= OL_MAX_SITES) raise(SW_ERR_RUNTIME, "oligo hits: a site list of 2^32 entries or more");
                     lists.emplace_back((size_t)n);
                     SW_HIP(hipMemcpyAsync(lists.back().p, buf.p, n * 8, hipMemcpyDeviceToDevice, stream));
                 }
@@ -689,46 +762,21 @@ void batch_oligo_hits(const sw_batch &b, const uint64_t *offsets, const char *bl
         }
     }
     SW_HIP(hipEventRecord(e1, stream));
-    // ---- the site list: all chunks' keys in one ascending order = (oligo, assembly, record, pos, strand) ----
-    if (want_sites && hits) {
-        DevArray<uint64_t> ka(hits), kb(hits);
-        uint64_t at = 0;
-        for (DevArray<uint64_t> &l : lists) {
-            SW_HIP(hipMemcpyAsync(ka.p + at, l.p, l.n * 8, hipMemcpyDeviceToDevice, stream));
-            at += l.n;
-        }
-        if (at != hits) raise(SW_ERR_RUNTIME, "internal error: the chunks' site lists do not add up");
-        uint64_t *kp = ka.p, *ap = kb.p;
-        sort_all_bits(kp, ap, hits, stream);
-        lists.clear();
-        if (kp != ka.p) std::swap(ka, kb);
-        o.keys = std::move(ka);
-        o.n_list = hits;
-        o.s_asm.alloc(hits);
-        o.s_rec.alloc(hits);
-        o.s_pos.alloc(hits);
-        launch_1d(k_ol_decode, hits, stream, (const uint64_t *)o.keys.p, runs.view(), o.s_asm.p, o.s_rec.p, o.s_pos.p);
-    }
+    if (want_sites && cnt.hits) finish_site_list(lists, cnt.hits, k_ol_decode<OL_SITE_IDX_SHIFT, OL_SITE_Q_SHIFT - OL_SITE_IDX_SHIFT>, runs.view(), stream, o);
     SW_HIP(hipEventRecord(e2, stream));
-    if (th && want_sites && hits) {
-        for (int f = 0; f < 3; ++f) o.s_sum[f].alloc(hits);
-        launch_1d(k_ol_thermo_sites, hits, stream, (const uint64_t *)o.keys.p, b.d_packed.p, (const uint32_t *)all_rows.p, model, o.s_sum[0].p, o.s_sum[1].p,
+    if (th && want_sites && cnt.hits) {
+        for (int f = 0; f < 3; ++f) o.s_sum[f].alloc(cnt.hits);
+        launch_1d(k_ol_thermo_sites, cnt.hits, stream, (const uint64_t *)o.keys.p, b.d_packed.p, (const uint32_t *)all_rows.p, model, o.s_sum[0].p, o.s_sum[1].p,
                   o.s_sum[2].p);
         SW_HIP(hipEventRecord(*tb, stream));
     }
-    SW_HIP(hipStreamSynchronize(stream));   // (the temporaries go back to the pool behind the kernels)
-    float ms = 0;
-    SW_HIP(hipEventElapsedTime(&ms, e0, e1));
-    o.ms[0] = std::max(0.0, (double)ms - best_ms);
-    SW_HIP(hipEventElapsedTime(&ms, e1, e2));
-    o.ms[1] = ms;
+    close_result(stream, e0, e1, e2, best_ms, cnt, o);
     o.thermo_ms[0] = best_ms;
-    if (th && want_sites && hits) {
+    if (th && want_sites && cnt.hits) {
+        float ms = 0;
         SW_HIP(hipEventElapsedTime(&ms, e2, *tb));
         o.thermo_ms[1] = ms;
     }
-    const uint64_t cn[8] = {windows, passes, chunks, launches, hits, grows, splits, comparisons};
-    memcpy(o.counters, cn, sizeof cn);
 }
 
 // ---- the route with indels ---------------------------------------------------------------------------------------------------------
@@ -761,32 +809,16 @@ void batch_oligo_edit(const sw_batch &b, const uint64_t *offsets, const char *bl
 {
     const HostBatch &h = b.host;
     const uint64_t n_asm = h.n_assemblies, cells = nq * n_asm;
-    if (h.rec_len.size() && !b.d_packed.p) raise(SW_ERR_VALUE, "oligo hits: the batch holds no packed bases (it must be resident)");
-    if ((uint64_t)h.packed_words32() * 16 >= OL_MAX_BASES) raise(SW_ERR_RUNTIME, "oligo hits: the batch has 2^43 bases or more");
-    o.nq = nq;
-    o.n_asm = n_asm;
-    o.max_mm = 0;
-    o.max_edits = d;
-    o.three_prime = three_prime;
-    o.has_sites = want_sites;
-    for (uint64_t q = 0; q < nq; ++q) o.lens.push_back((uint32_t)(offsets[q + 1] - offsets[q]));
-    for (int f = 0; f < 8; ++f) {
-        o.field[f].alloc(cells);
-        if (cells) SW_HIP(hipMemsetAsync(o.field[f].p, f ? 0xFF : 0, cells * 4, stream));
-    }
+    start_result(b, offsets, nq, 0, d, three_prime, want_sites, 8, stream, o);
     const uint32_t k = lmin - d;   // a site spans L - d bases or more
     RunTiles T;
     build_run_tiles(h, k, "oligo hits", T);
     std::vector<uint64_t> asm_lanes(n_asm + 1, 0);   // lanes with an end, of the assemblies before a
     for (uint64_t r = 0; r < T.n_runs; ++r) asm_lanes[T.run_asm[r] + 1] += (T.run_nk[r] + KW_L - 1) / KW_L;
     for (uint64_t a = 0; a < n_asm; ++a) asm_lanes[a + 1] += asm_lanes[a];
-    uint64_t group = OL_GROUP, budget = OL_BUFFER_BYTES;
-    if (const char *e = SW_TEST_GETENV("SEQWIN_AMD_OLIGO_GROUP")) group = std::min<uint64_t>(std::max<uint64_t>(env_u64(e, group), 1), OL_GROUP);
-    if (const char *e = SW_TEST_GETENV("SEQWIN_AMD_OLIGO_BUFFER_KB")) budget = env_u64(e, budget >> 10) << 10;
-    group = std::min<uint64_t>(group, nq);
-    uint64_t cap = std::min<uint64_t>(std::max<uint64_t>(budget / 8, 1), OL_MAX_SITES);
-    const uint32_t blocks_max = launch_blocks("SEQWIN_AMD_OLIGO_MAX_BLOCKS");
-    uint64_t passes = 0, chunks = 0, launches = 0, hits = 0, grows = 0, splits = 0, windows = 0, comparisons = 0, steps = 0;
+    auto [group, cap, blocks_max] = chunk_sizes(nq);   // (cap doubles with the buffer)
+    OligoCounts cnt;
+    uint64_t steps = 0;
     double resolve_ms = 0;
     std::vector<DevArray<uint64_t>> lists;
     Event e0, e1, e2, ra, rb;
@@ -804,7 +836,7 @@ void batch_oligo_edit(const sw_batch &b, const uint64_t *offsets, const char *bl
         g.cursor = d_cursor.p;
         const BestFields bf{o.field[1].p, o.field[2].p, o.field[3].p, o.field[4].p, o.field[5].p, o.field[6].p, o.field[7].p};
         uint64_t rows = n_asm;
-        for (uint64_t q0 = 0; q0 < nq; q0 += group, ++passes) {
+        for (uint64_t q0 = 0; q0 < nq; q0 += group, ++cnt.passes) {
             const uint64_t qn = std::min<uint64_t>(group, nq - q0);
             uint64_t len_sum = 0;
             for (uint64_t q = 0; q < qn; ++q) {
@@ -820,30 +852,22 @@ void batch_oligo_edit(const sw_batch &b, const uint64_t *offsets, const char *bl
                 g.buf = buf.p;
                 g.cap = cap;
                 g.v = runs.view(T.asm_tile_off[a0], T.asm_tile_off[a1]);
-                launches += launch_tiles(k_ole_scan, g, blocks_max, stream);
+                cnt.launches += launch_tiles(k_ole_scan, g, blocks_max, stream);
                 unsigned long long n = 0;
                 SW_HIP(hipMemcpyAsync(&n, d_cursor.p, 8, hipMemcpyDeviceToHost, stream));
                 SW_HIP(hipStreamSynchronize(stream));   // (the rows of the host are free again, too)
                 if (n > cap) {
-                    if (a1 - a0 > 1) {   // redone in two halves: the first now, the second is the next chunk
-                        rows = (a1 - a0 + 1) / 2;
-                        ++splits;
-                    } else {             // one assembly above the budget: the buffer doubles
-                        if (cap >= OL_MAX_SITES) raise(SW_ERR_RUNTIME, "oligo hits: assembly %llu alone has 2^32 sites or more", (unsigned long long)a0);
-                        cap = std::min<uint64_t>(cap * 2, OL_MAX_SITES);
-                        buf.alloc(cap);
-                        ++grows;
-                    }
+                    overflow_step(a0, a1, rows, cap, buf, cnt);
                     continue;
                 }
                 const uint64_t ends = T.asm_kmers[a1] - T.asm_kmers[a0], lanes = asm_lanes[a1] - asm_lanes[a0];
-                hits += n;
-                windows += ends;
-                comparisons += ends * 2 * qn;
+                cnt.hits += n;
+                cnt.windows += ends;
+                cnt.comparisons += ends * 2 * qn;
                 steps += 2 * (qn * ends + lanes * (len_sum + qn * 3 * d - qn));   // a lane steps L + 3 d - 1 bases more than it has ends
-                ++chunks;
+                ++cnt.chunks;
                 if (n) {
-                    if (want_sites && hits >= OL_MAX_SITES) raise(SW_ERR_RUNTIME, "oligo hits: a site list of 2^32 entries or more");
+                    if (want_sites && cnt.hits >= OL_MAX_SITES) raise(SW_ERR_RUNTIME, "oligo hits: a site list of 2^32 entries or more");
                     SW_HIP(hipEventRecord(ra, stream));
                     launch_1d(k_ole_resolve, n, stream, buf.p, (const uint32_t *)tab.p, (uint32_t)q0, runs.view(), k, d, three_prime, n_asm, o.field[0].p, best.p);
                     SW_HIP(hipEventRecord(rb, stream));
@@ -863,38 +887,12 @@ void batch_oligo_edit(const sw_batch &b, const uint64_t *offsets, const char *bl
         }
     }
     SW_HIP(hipEventRecord(e1, stream));
-    // ---- the site list: all chunks' keys in one ascending order = (oligo, assembly, record, pos, end, strand) ----
-    if (want_sites && hits) {
-        DevArray<uint64_t> ka(hits), kb(hits);
-        uint64_t at = 0;
-        for (DevArray<uint64_t> &l : lists) {
-            SW_HIP(hipMemcpyAsync(ka.p + at, l.p, l.n * 8, hipMemcpyDeviceToDevice, stream));
-            at += l.n;
-        }
-        if (at != hits) raise(SW_ERR_RUNTIME, "internal error: the chunks' site lists do not add up");
-        uint64_t *kp = ka.p, *ap = kb.p;
-        sort_all_bits(kp, ap, hits, stream);
-        lists.clear();
-        if (kp != ka.p) std::swap(ka, kb);
-        o.keys = std::move(ka);
-        o.n_list = hits;
-        o.s_asm.alloc(hits);
-        o.s_rec.alloc(hits);
-        o.s_pos.alloc(hits);
-        launch_1d(k_ole_decode, hits, stream, (const uint64_t *)o.keys.p, runs.view(), o.s_asm.p, o.s_rec.p, o.s_pos.p);
-    }
+    if (want_sites && cnt.hits) finish_site_list(lists, cnt.hits, k_ol_decode<OLE_IDX_SHIFT, OLE_SITE_Q_SHIFT - OLE_IDX_SHIFT>, runs.view(), stream, o);
     SW_HIP(hipEventRecord(e2, stream));
-    SW_HIP(hipStreamSynchronize(stream));   // (the temporaries go back to the pool behind the kernels)
-    float ms = 0;
-    SW_HIP(hipEventElapsedTime(&ms, e0, e1));
-    o.ms[0] = std::max(0.0, (double)ms - resolve_ms);
-    SW_HIP(hipEventElapsedTime(&ms, e1, e2));
-    o.ms[1] = ms;
+    close_result(stream, e0, e1, e2, resolve_ms, cnt, o);
     o.resolve_ms = resolve_ms;
-    const uint64_t cn[8] = {windows, passes, chunks, launches, hits, grows, splits, comparisons};
-    memcpy(o.counters, cn, sizeof cn);
     o.edit_counters[0] = steps;
-    o.edit_counters[1] = hits;
+    o.edit_counters[1] = cnt.hits;
 }
 
 }  // namespace
@@ -909,13 +907,9 @@ int sw_batch_oligo_hits(const sw_batch *batch, const uint64_t *offsets, const ch
 {
     return guarded([&] {
         const uint32_t lmin = check_oligos(offsets, blob, n_oligos, max_mismatch, three_prime);
-        if (!batch || !out) raise(SW_ERR_VALUE, "oligo hits: a NULL handle or array");
-        require_device(batch->device, "the batch");
-        StreamScope scope((hipStream_t)stream);
-        std::unique_ptr<sw_oligos> o(new sw_oligos);
-        o->device = batch->device;
-        batch_oligo_hits(*batch, offsets, blob, n_oligos, lmin, (uint32_t)max_mismatch, (uint32_t)three_prime, want_sites != 0, (hipStream_t)stream, *o);
-        *out = o.release();
+        make_oligos(batch, stream, out, [&](sw_oligos &o) {
+            batch_oligo_hits(*batch, offsets, blob, n_oligos, lmin, (uint32_t)max_mismatch, (uint32_t)three_prime, want_sites != 0, (hipStream_t)stream, o);
+        });
     });
 }
 
@@ -937,17 +931,11 @@ int sw_oligos_block(const sw_oligos *h, uint64_t field, uint64_t r0, uint64_t r1
         if (field > 7)
             raise(SW_ERR_VALUE, "oligo hits: field %llu; 0 n_sites, 1 best_mm, 2 best_record, 3 best_pos, 4 best_strand, 5 best_end, 6 best_mismatch, 7 best_gaps",
                   (unsigned long long)field);
-        if (r0 > r1 || r1 > h->nq || c0 > c1 || c1 > h->n_asm)
-            raise(SW_ERR_VALUE, "oligo hits: rows [%llu, %llu) x columns [%llu, %llu) lie outside the %llu oligos x %llu assemblies", (unsigned long long)r0,
-                  (unsigned long long)r1, (unsigned long long)c0, (unsigned long long)c1, (unsigned long long)h->nq, (unsigned long long)h->n_asm);
-        const uint64_t nr = r1 - r0, nc = c1 - c0;
-        if (!nr || !nc) return;
-        if (!out) raise(SW_ERR_VALUE, "oligo hits: a NULL handle or array");
-        require_device(h->device, "the oligo hits");
         // a Hamming result keeps no end, mismatch or gaps: they follow from pos + L, mm and 0
         const bool derived = field > 4 && h->max_edits < 0;
         const uint64_t src = !derived ? field : field == 5 ? 3 : 1;
-        SW_HIP(hipMemcpy2D(out, nc * 4, h->field[src].p + r0 * h->n_asm + c0, h->n_asm * 4, nc * 4, nr, hipMemcpyDeviceToHost));
+        export_cells("oligo hits", "oligos", h->device, "the oligo hits", h->field[src].p, h->nq, h->n_asm, r0, r1, c0, c1, out);
+        const uint64_t nr = r1 - r0, nc = c1 - c0;
         if (derived && field != 6)
             for (uint64_t r = 0; r < nr; ++r)
                 for (uint64_t c = 0; c < nc; ++c)
@@ -1031,13 +1019,9 @@ int sw_batch_oligo_hits_edit(const sw_batch *batch, const uint64_t *offsets, con
     return guarded([&] {
         const uint32_t lmin = check_oligos(offsets, blob, n_oligos, 0, three_prime);
         check_edits(lmin, max_edits, three_prime);
-        if (!batch || !out) raise(SW_ERR_VALUE, "oligo hits: a NULL handle or array");
-        require_device(batch->device, "the batch");
-        StreamScope scope((hipStream_t)stream);
-        std::unique_ptr<sw_oligos> o(new sw_oligos);
-        o->device = batch->device;
-        batch_oligo_edit(*batch, offsets, blob, n_oligos, lmin, (uint32_t)max_edits, (uint32_t)three_prime, want_sites != 0, (hipStream_t)stream, *o);
-        *out = o.release();
+        make_oligos(batch, stream, out, [&](sw_oligos &o) {
+            batch_oligo_edit(*batch, offsets, blob, n_oligos, lmin, (uint32_t)max_edits, (uint32_t)three_prime, want_sites != 0, (hipStream_t)stream, o);
+        });
     });
 }
 
@@ -1075,13 +1059,9 @@ int sw_batch_oligo_hits_thermo(const sw_batch *batch, const uint64_t *offsets, c
         const uint32_t lmin = check_oligos(offsets, blob, n_oligos, max_mismatch, three_prime);
         const ThermoModel th{stack, end, init, no_threshold ? INT32_MAX : (int32_t)std::min<int64_t>(std::max<int64_t>(max_dg, INT32_MIN), INT32_MAX)};
         check_model(th);
-        if (!batch || !out) raise(SW_ERR_VALUE, "oligo hits: a NULL handle or array");
-        require_device(batch->device, "the batch");
-        StreamScope scope((hipStream_t)stream);
-        std::unique_ptr<sw_oligos> o(new sw_oligos);
-        o->device = batch->device;
-        batch_oligo_hits(*batch, offsets, blob, n_oligos, lmin, (uint32_t)max_mismatch, (uint32_t)three_prime, want_sites != 0, (hipStream_t)stream, *o, &th);
-        *out = o.release();
+        make_oligos(batch, stream, out, [&](sw_oligos &o) {
+            batch_oligo_hits(*batch, offsets, blob, n_oligos, lmin, (uint32_t)max_mismatch, (uint32_t)three_prime, want_sites != 0, (hipStream_t)stream, o, &th);
+        });
     });
 }
 
@@ -1093,15 +1073,8 @@ int sw_oligos_thermo_block(const sw_oligos *h, uint64_t field, uint64_t r0, uint
         if (field > 7)
             raise(SW_ERR_VALUE, "oligo hits: thermo field %llu; 0 n_stable, 1 stable_dg, 2 stable_dh, 3 stable_ds, 4 stable_record, 5 stable_pos, 6 stable_strand, 7 stable_mm",
                   (unsigned long long)field);
-        if (r0 > r1 || r1 > h->nq || c0 > c1 || c1 > h->n_asm)
-            raise(SW_ERR_VALUE, "oligo hits: rows [%llu, %llu) x columns [%llu, %llu) lie outside the %llu oligos x %llu assemblies", (unsigned long long)r0,
-                  (unsigned long long)r1, (unsigned long long)c0, (unsigned long long)c1, (unsigned long long)h->nq, (unsigned long long)h->n_asm);
-        const uint64_t nr = r1 - r0, nc = c1 - c0;
-        if (!nr || !nc) return;
-        if (!out) raise(SW_ERR_VALUE, "oligo hits: a NULL handle or array");
-        require_device(h->device, "the oligo hits");
         const void *src = field == 0 ? (const void *)h->n_stable.p : field < 4 ? (const void *)h->stable_sum[field - 1].p : (const void *)h->stable_at[field - 4].p;
-        SW_HIP(hipMemcpy2D(out, nc * 4, (const char *)src + (r0 * h->n_asm + c0) * 4, h->n_asm * 4, nc * 4, nr, hipMemcpyDeviceToHost));
+        export_cells("oligo hits", "oligos", h->device, "the oligo hits", src, h->nq, h->n_asm, r0, r1, c0, c1, out);
     });
 }
 

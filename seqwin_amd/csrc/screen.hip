@@ -594,14 +594,7 @@ int sw_screen_counts(const sw_screen *h, uint64_t r0, uint64_t r1, uint64_t c0, 
 {
     return guarded([&] {
         if (!h) raise(SW_ERR_VALUE, "screen: a NULL handle");
-        if (r0 > r1 || r1 > h->nq || c0 > c1 || c1 > h->n_asm)
-            raise(SW_ERR_VALUE, "screen: rows [%llu, %llu) x columns [%llu, %llu) lie outside the %llu queries x %llu assemblies", (unsigned long long)r0,
-                  (unsigned long long)r1, (unsigned long long)c0, (unsigned long long)c1, (unsigned long long)h->nq, (unsigned long long)h->n_asm);
-        const uint64_t nr = r1 - r0, nc = c1 - c0;
-        if (!nr || !nc) return;
-        if (!counts) raise(SW_ERR_VALUE, "screen: a NULL handle or array");
-        require_device(h->device, "the screen");
-        SW_HIP(hipMemcpy2D(counts, nc * 4, h->counts.p + r0 * h->n_asm + c0, h->n_asm * 4, nc * 4, nr, hipMemcpyDeviceToHost));
+        export_cells("screen", "queries", h->device, "the screen", h->counts.p, h->nq, h->n_asm, r0, r1, c0, c1, counts);
     });
 }
 

@@ -950,6 +950,16 @@ def _block_range(r, n: int):
     return int(lo), int(hi)
 
 
+def _cell_block(fn, handle, field, n_rows: int, n_cols: int, rows, cols, dtype=np.uint32) -> np.ndarray:
+    """``rows`` x ``cols`` of a ``[n_rows][n_cols]`` table of 32-bit cells, copied out by the library's block export ``fn``;
+    ``field`` selects the table (None: ``fn`` takes none)."""
+    (r0, r1), (c0, c1) = _block_range(rows, n_rows), _block_range(cols, n_cols)
+    out = np.empty((max(r1 - r0, 0), max(c1 - c0, 0)), dtype)
+    which = () if field is None else (c_u64(field),)
+    check(fn(handle, *which, c_u64(r0), c_u64(r1), c_u64(c0), c_u64(c1), _ptr(out)))
+    return out
+
+
 class MinHash:
     """MinHash sketches of a set of assemblies, resident on the device (:meth:`Batch.minhash`, :meth:`from_sketches`), and the
     pair counts ``mash dist`` derives from them: what ``Assemblies.mash`` (src/seqwin/assemblies.py:76-99) gets from the Mash
@@ -1088,10 +1098,7 @@ class Screen:
     def counts(self, rows=None, cols=None) -> np.ndarray:
         """uint32[rows, cols]: how many of the query's distinct canonical k-mers occur in the assembly."""
         nq, na, _, _ = self.sizes()
-        (r0, r1), (c0, c1) = _block_range(rows, nq), _block_range(cols, na)
-        out = np.empty((max(r1 - r0, 0), max(c1 - c0, 0)), np.uint32)
-        check(lib.sw_screen_counts(self._h, c_u64(r0), c_u64(r1), c_u64(c0), c_u64(c1), _ptr(out)))
-        return out
+        return _cell_block(lib.sw_screen_counts, self._h, None, nq, na, rows, cols)
 
     def containment(self, rows=None, cols=None) -> np.ndarray:
         """float64[rows, cols]: ``counts / n_kmers``; ``nan`` for a query without a k-mer."""
@@ -1232,10 +1239,7 @@ class OligoHits:
 
     def _block(self, field: int, rows, cols) -> np.ndarray:
         nq, na, _, _ = self.sizes()
-        (r0, r1), (c0, c1) = _block_range(rows, nq), _block_range(cols, na)
-        out = np.empty((max(r1 - r0, 0), max(c1 - c0, 0)), np.uint32)
-        check(lib.sw_oligos_block(self._h, c_u64(field), c_u64(r0), c_u64(r1), c_u64(c0), c_u64(c1), _ptr(out)))
-        return out
+        return _cell_block(lib.sw_oligos_block, self._h, field, nq, na, rows, cols)
 
     def n_sites(self, rows=None, cols=None) -> np.ndarray:
         """uint32[rows, cols]: the hits of the oligo in the assembly, both strands together; 0: none."""
@@ -1272,10 +1276,7 @@ class OligoHits:
         if not self.thermo:
             raise ValueError("these oligo hits were made without thermo=")
         nq, na, _, _ = self.sizes()
-        (r0, r1), (c0, c1) = _block_range(rows, nq), _block_range(cols, na)
-        out = np.empty((max(r1 - r0, 0), max(c1 - c0, 0)), dtype)
-        check(lib.sw_oligos_thermo_block(self._h, c_u64(field), c_u64(r0), c_u64(r1), c_u64(c0), c_u64(c1), _ptr(out)))
-        return out
+        return _cell_block(lib.sw_oligos_thermo_block, self._h, field, nq, na, rows, cols, dtype)
 
     def n_stable(self, rows=None, cols=None) -> np.ndarray:
         """uint32[rows, cols]: the hits with ``dg <= max_dg`` (every hit without a ``max_dg``).  This and the ``stable_*`` fields:
@@ -1563,10 +1564,7 @@ class BestHits:
 
     def _block(self, field: int, rows, cols) -> np.ndarray:
         nq, na, _, _ = self.sizes()
-        (r0, r1), (c0, c1) = _block_range(rows, nq), _block_range(cols, na)
-        out = np.empty((max(r1 - r0, 0), max(c1 - c0, 0)), np.uint32)
-        check(lib.sw_hits_block(self._h, c_u64(field), c_u64(r0), c_u64(r1), c_u64(c0), c_u64(c1), _ptr(out)))
-        return out
+        return _cell_block(lib.sw_hits_block, self._h, field, nq, na, rows, cols)
 
     def seeds(self, rows=None, cols=None) -> np.ndarray:
         """uint32[rows, cols]: the winner's vote (hits of its band and the next); 0: no hit."""
@@ -1588,10 +1586,7 @@ class BestHits:
         if not self._aligned:
             raise ValueError("these best hits were made without align=True")
         nq, na, _, _ = self.sizes()
-        (r0, r1), (c0, c1) = _block_range(rows, nq), _block_range(cols, na)
-        out = np.empty((max(r1 - r0, 0), max(c1 - c0, 0)), np.uint32)
-        check(lib.sw_hits_align_block(self._h, c_u64(field), c_u64(r0), c_u64(r1), c_u64(c0), c_u64(c1), _ptr(out)))
-        return out
+        return _cell_block(lib.sw_hits_align_block, self._h, field, nq, na, rows, cols)
 
     def start(self, rows=None, cols=None) -> np.ndarray:
         """uint32[rows, cols]: where the located copy starts in its record; it is ``[start, end)``."""
@@ -1633,10 +1628,7 @@ class BestHits:
         if not self._local:
             raise ValueError("these best hits were made without local=True")
         nq, na, _, _ = self.sizes()
-        (r0, r1), (c0, c1) = _block_range(rows, nq), _block_range(cols, na)
-        out = np.empty((max(r1 - r0, 0), max(c1 - c0, 0)), np.uint32)
-        check(lib.sw_hits_local_block(self._h, c_u64(field), c_u64(r0), c_u64(r1), c_u64(c0), c_u64(c1), _ptr(out)))
-        return out
+        return _cell_block(lib.sw_hits_local_block, self._h, field, nq, na, rows, cols)
 
     def score(self, rows=None, cols=None) -> np.ndarray:
         """uint32[rows, cols]: the raw score of the winner's optimal local alignment on its window (0: nothing matches)."""
@@ -1683,10 +1675,7 @@ class BestHits:
         if not self._loci:
             raise ValueError("these best hits were made without loci=True")
         nq, na, _, _ = self.sizes()
-        (r0, r1), (c0, c1) = _block_range(rows, nq), _block_range(cols, na)
-        out = np.empty((max(r1 - r0, 0), max(c1 - c0, 0)), np.uint32)
-        check(lib.sw_hits_loci_block(self._h, c_u64(field), c_u64(r0), c_u64(r1), c_u64(c0), c_u64(c1), _ptr(out)))
-        return out
+        return _cell_block(lib.sw_hits_loci_block, self._h, field, nq, na, rows, cols)
 
     def n_loci(self, rows=None, cols=None) -> np.ndarray:
         """uint32[rows, cols]: the pair's loci with ``min_seeds`` or more seeds, duplicates counted once; 0: none."""
