@@ -821,6 +821,45 @@ int sw_oligos_thermo_stats(const sw_oligos *h, uint64_t *stable_hits, double *ms
 /* (no counterpart in the reference) */
 void sw_oligos_free(sw_oligos *h);
 
+/* ---- amplicons: the products of primer pairs, and the probes inside them, over a site list (csrc/amplicons.hip, DESIGN.md section
+ * 3.2p; tests/tools/amplicons_host.py restates it) ----
+ * None of this has a counterpart in the reference, and it is no in-silico PCR tool.  Exact, in integers, on the site list of a
+ * sw_oligos made with want_sites.  A site is (oligo, assembly, record, pos, end, strand, d): on a Hamming result end = pos + L and
+ * d = mm, on a result with max_edits the site's own end and dist.  For pair i = (f, r): orientation + (0) joins a site of f on strand
+ * 0 at pf with a site of r on strand 1 of the same record with pos_r >= pf, the product is [pf, end_r); orientation - (1) is the same
+ * with f and r exchanged; with f == r only + is formed.  A product is kept iff min_len <= end - start <= max_len; every combination
+ * counts; a product may span invalid bases and never spans two records.  Without no_threshold a PRIMER site takes part only if its
+ * dg <= max_dg (the result must carry a model); probe sites are never filtered.  With a probe p, n_probe of a product is the number
+ * of sites of p in that record, on either strand, with end_first <= pos_p and end_p <= pos_last: the probe lies strictly between the
+ * two primer sites.  Without a probe n_probe is 0. */
+typedef struct sw_amplicons sw_amplicons; /* opaque: the device-resident [n_pairs][n_assemblies] counts of one call, and the products */
+/* (no counterpart in the reference)  pairs[n_pairs][2] = (f, r), indices into the call's oligos; probes: NULL, or [n_pairs] with an
+ * oligo index or 0xFFFFFFFF (a pair without a probe).  A pair listed twice is two rows.  0 pairs or more than 65 536, an index
+ * outside the call's oligos, min_len > max_len, min_len < 1, a result made without sites, no_threshold == 0 on a result without a
+ * model: SW_ERR_VALUE before a device is touched.  2^32 products or more (counted in 64 bits): SW_ERR_RUNTIME.  want_products != 0
+ * also keeps the list of products.  The result does not depend on `oligos` after the call returns. */
+int sw_oligos_amplicons(const sw_oligos *oligos, const uint32_t *pairs, const uint32_t *probes, uint64_t n_pairs, uint64_t min_len,
+                        uint64_t max_len, int want_products, int64_t max_dg, int no_threshold, void *stream, sw_amplicons **out);
+/* (no counterpart in the reference)  Pairs, assemblies, min_len, max_len of the call (any pointer may be NULL). */
+int sw_amplicons_sizes(const sw_amplicons *h, uint64_t *n_pairs, uint64_t *n_assemblies, uint64_t *min_len, uint64_t *max_len);
+/* (no counterpart in the reference)  sw_oligos_block for one field: 0 n_amplicons, the products of the pair in the assembly; 1
+ * n_detected, those of them with n_probe >= 1 (zero for a pair without a probe). */
+int sw_amplicons_block(const sw_amplicons *h, uint64_t field, uint64_t r0, uint64_t r1, uint64_t c0, uint64_t c1, uint32_t *out);
+/* (no counterpart in the reference)  Entries of the list of products.  This and sw_amplicons_products: SW_ERR_VALUE for a result made
+ * without it. */
+int sw_amplicons_products_size(const sw_amplicons *h, uint64_t *n_products);
+/* (no counterpart in the reference)  Every product, ascending by (pair, assembly, record, start, end, orientation, mm_f, mm_r) -- rows
+ * equal in all eight keep the order (first site, last site) of the site list --: cell_offsets[n_pairs * n_assemblies + 1] and the
+ * list's nine columns, n_products entries each.  mm_f / mm_r are d of the site of f / r. */
+int sw_amplicons_products(const sw_amplicons *h, uint64_t *cell_offsets, uint32_t *pair, uint32_t *assembly, uint32_t *record, uint32_t *start,
+                          uint32_t *end, uint32_t *orientation, uint32_t *mm_f, uint32_t *mm_r, uint32_t *n_probe);
+/* (no counterpart in the reference)  counters[6] = { items (first sites offered to a pair and orientation), items on the wave route,
+ * partners visited, products, detected products, kernel launches }; ms[3] = { count, emit, order of the list } (HIP events; the last
+ * two are 0 without the list). */
+int sw_amplicons_stats(const sw_amplicons *h, uint64_t *counters, double *ms);
+/* (no counterpart in the reference) */
+void sw_amplicons_free(sw_amplicons *h);
+
 /* ---- multi-GPU merge (one process per GPU; the exchange itself is done by the host side with
  *      torch.distributed / RCCL on the device buffers below).  Together these replace
  *      merge_thread_graphs (cpp/src/seqwin/build_internals.cpp:295-392) across GPUs. -------------- */

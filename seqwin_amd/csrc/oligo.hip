@@ -44,6 +44,7 @@
 #include "screen_core.hpp"
 #include "oligo_edit_core.hpp"
 #include "oligo_thermo_core.hpp"
+#include "oligo_result.hpp"
 
 namespace sw {
 namespace {
@@ -56,7 +57,7 @@ constexpr uint64_t OL_MAX_BASES = 1ull << 43;          // the batch-wide base in
 constexpr uint64_t OL_MAX_SITES = 1ull << 32;
 constexpr unsigned long long OL_NONE = ~0ull;
 // best-site key: mm << 58 | base index << 1 | strand; site key: oligo << 48 | base index << 5 | strand << 4 | mm
-constexpr uint32_t OL_BEST_MM_SHIFT = 58, OL_SITE_Q_SHIFT = 48, OL_SITE_IDX_SHIFT = 5;
+constexpr uint32_t OL_BEST_MM_SHIFT = 58, OL_SITE_IDX_SHIFT = 5;   // (OL_SITE_Q_SHIFT: oligo_result.hpp)
 // stable-site key: (dg + 2^19) << 44 | base index << 1 | strand -- 20 + 43 + 1 bits
 constexpr uint32_t OL_STABLE_DG_SHIFT = 44;
 static_assert(OL_MAX_BASES == 1ull << (OL_STABLE_DG_SHIFT - 1), "the stable key keeps the base index below the biased dg");
@@ -303,7 +304,7 @@ constexpr uint64_t OLE_IDX_MASK = (1ull << 43) - 1;
 constexpr uint32_t OLE_CAND_Q_SHIFT = 44, OLE_CAND_STRAND_SHIFT = 43;
 // site key: oligo << 52 | index of pos << 9 | (end - pos - (L - d)) << 5 | strand << 4 | code;  code = 5 t + mismatch, gaps = |end - pos - L| + 2 t
 // best key: dist << 61 | index of pos << 9 | strand << 8 | (end - pos - (L - d)) << 4 | code
-constexpr uint32_t OLE_SITE_Q_SHIFT = 52, OLE_IDX_SHIFT = 9, OLE_BEST_DIST_SHIFT = 61;
+constexpr uint32_t OLE_IDX_SHIFT = 9, OLE_BEST_DIST_SHIFT = 61;   // (OLE_SITE_Q_SHIFT: oligo_result.hpp)
 
 struct EditScanArgs {
     RunView v;                       // the tiles of this launch (runs of k = lmin - d bases or more)
@@ -481,30 +482,6 @@ void pattern_rows(const char *text, uint32_t len, uint32_t clamp, uint32_t *rows
 
 }  // namespace
 }  // namespace sw
-
-struct sw_oligos {
-    int device = 0;
-    uint64_t nq = 0, n_asm = 0, max_mm = 0, three_prime = 0;
-    int64_t max_edits = -1;                // -1: a Hamming result
-    std::vector<uint32_t> lens;            // [nq] the oligos' lengths
-    sw::DevArray<uint32_t> field[8];       // [nq][n_asm] n_sites, best_mm (an edit result: best_dist), best_record, best_pos, best_strand;
-                                           // an edit result only: best_end, best_mismatch, best_gaps
-    bool has_sites = false;
-    uint64_t n_list = 0;
-    sw::DevArray<uint64_t> keys;           // [n_list] the site keys, ascending
-    sw::DevArray<uint32_t> s_asm, s_rec, s_pos;
-    uint64_t counters[8] = {};             // sw_oligos_stats
-    double ms[2] = {};                     // scan, order
-    uint64_t edit_counters[2] = {};        // sw_oligos_edit_stats: DP steps, candidates resolved
-    double resolve_ms = 0;
-    // a Hamming result made with a thermodynamic model (section 3.2o); nothing of it is allocated without one
-    bool thermo = false;
-    sw::DevArray<uint32_t> n_stable;       // [nq][n_asm]
-    sw::DevArray<int32_t> stable_sum[3];   // [nq][n_asm] stable_dg, stable_dh, stable_ds
-    sw::DevArray<uint32_t> stable_at[4];   // [nq][n_asm] stable_record, stable_pos, stable_strand, stable_mm
-    sw::DevArray<int32_t> s_sum[3];        // [n_list] dh, ds, dg of the sites
-    double thermo_ms[2] = {};              // k_ol_thermo_best, k_ol_thermo_sites
-};
 
 namespace sw {
 namespace {

@@ -1368,9 +1368,139 @@ class OligoHits:
             d.update(stable_hits=int(n3.value), thermo_ms=ms3[0], site_thermo_ms=ms3[1])
         return d
 
+    def amplicons(self, pairs, min_len: int, max_len: int, probes=None, products: bool = True, max_dg=None, stream: int = 0) -> "Amplicons":
+        """The products of primer pairs over the resident site list, and the probes inside them (csrc/amplicons.hip, DESIGN.md
+        section 3.2p): :func:`seqwin_amd.oligos.amplicons` on the device, with probes and a ``dg`` filter.  ``pairs`` is an (n, 2)
+        array of ``(f, r)`` oligo indices (1..65 536 rows; a pair listed twice is two rows).  Orientation ``+`` (0): a site of f on
+        strand 0 at ``pf`` and a site of r on strand 1 of the same record with ``pos_r >= pf``, product ``[pf, end_r)``; ``-`` (1):
+        f and r exchanged; with ``f == r`` only ``+``.  A product is kept iff ``min_len <= end - start <= max_len``; every
+        combination counts.  ``probes`` (None, or one entry per pair: an oligo index, or None / ``NO_PROBE`` for a pair without
+        one): ``n_probe`` of a product counts the probe's sites in that record, on either strand, that lie strictly between the two
+        primer sites (``end_first <= pos_p`` and ``end_p <= pos_last``).  ``max_dg`` (cal/mol; the hits must have been made with
+        ``thermo=``): a PRIMER site takes part only if its ``dg <= max_dg``; probe sites are not filtered.  ``products=False``
+        keeps the two count matrices only.  ValueError for anything else, before the library is called."""
+        if not self._sites:
+            raise ValueError("these oligo hits were made without sites=True")
+        nq = len(self.lengths)
+        try:
+            p = np.asarray(pairs, np.int64).reshape(-1, 2)
+        except (TypeError, ValueError):
+            raise ValueError("pairs must be an (n, 2) array of oligo indices") from None
+        if not 1 <= len(p) <= AMPLICON_MAX_PAIRS:
+            raise ValueError(f"{len(p)} pairs; 1..{AMPLICON_MAX_PAIRS} are taken")
+        if p.min() < 0 or p.max() >= nq:
+            raise ValueError(f"a pair names an oligo outside the call's {nq}")
+        if int(min_len) != min_len or int(max_len) != max_len or min_len < 1:
+            raise ValueError(f"min_len and max_len must be integers of 1 or more (got {min_len!r}, {max_len!r})")
+        if min_len > max_len:
+            raise ValueError(f"min_len {min_len} exceeds max_len {max_len}")
+        pr = None
+        if probes is not None:
+            pl = [NO_PROBE if x is None else int(x) for x in probes]
+            if len(pl) != len(p):
+                raise ValueError(f"{len(pl)} probes for {len(p)} pairs")
+            if any(x != NO_PROBE and not 0 <= x < nq for x in pl):
+                raise ValueError(f"a probe names an oligo outside the call's {nq}")
+            pr = np.asarray(pl, np.uint32)
+        if max_dg is not None:
+            if not self.thermo:
+                raise ValueError("max_dg needs oligo hits made with thermo=")
+            try:
+                whole = int(max_dg) == max_dg and -2 ** 31 <= int(max_dg) < 2 ** 31
+            except (TypeError, ValueError, OverflowError):
+                whole = False
+            if not whole:
+                raise ValueError(f"max_dg must be an integer of cal/mol that fits int32 (got {max_dg!r})")
+        p32 = np.ascontiguousarray(p, np.uint32)
+        h = c_vp()
+        check(lib.sw_oligos_amplicons(self._h, _ptr(p32), None if pr is None else _ptr(pr), c_u64(len(p32)), c_u64(int(min_len)), c_u64(int(max_len)),
+                                      ctypes.c_int(1 if products else 0), ctypes.c_int64(0 if max_dg is None else int(max_dg)),
+                                      ctypes.c_int(1 if max_dg is None else 0), c_vp(stream), ctypes.byref(h)))
+        return Amplicons(h, bool(products))
+
     def close(self) -> None:
         if self._h:
             lib.sw_oligos_free(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+AMPLICON_MAX_PAIRS = 65536
+NO_PROBE = 0xFFFFFFFF
+PRODUCT_FIELDS = ("pair", "assembly", "record", "start", "end", "orientation", "mm_f", "mm_r", "n_probe")
+
+
+class Amplicons:
+    """The products of primer pairs in every assembly, resident on the device (:meth:`OligoHits.amplicons`; csrc/amplicons.hip,
+    DESIGN.md section 3.2p): per (pair, assembly) ``n_amplicons`` and ``n_detected``, the products with at least one probe site
+    between the primers (zero for a pair without a probe), and -- made with ``products=True`` -- the list of products.  It has no
+    counterpart in the reference.  It does not depend on the :class:`OligoHits` it came from.  ``rows`` (pairs) / ``cols``
+    (assemblies) as for :class:`OligoHits`; either matrix goes to :func:`seqwin_amd.oligos.assay_summary` unchanged."""
+
+    def __init__(self, handle: c_vp, products: bool):
+        self._h = handle
+        self._products = products
+
+    def sizes(self):
+        """(pairs, assemblies, min_len, max_len)"""
+        v = [c_u64() for _ in range(4)]
+        check(lib.sw_amplicons_sizes(self._h, *[ctypes.byref(x) for x in v]))
+        return tuple(x.value for x in v)
+
+    def _block(self, field: int, rows, cols) -> np.ndarray:
+        n, na, _, _ = self.sizes()
+        return _cell_block(lib.sw_amplicons_block, self._h, field, n, na, rows, cols)
+
+    def n_amplicons(self, rows=None, cols=None) -> np.ndarray:
+        """uint32[rows, cols]: the products of the pair in the assembly, both orientations together."""
+        return self._block(0, rows, cols)
+
+    def n_detected(self, rows=None, cols=None) -> np.ndarray:
+        """uint32[rows, cols]: the products with ``n_probe >= 1``."""
+        return self._block(1, rows, cols)
+
+    def products(self) -> dict:
+        """Every product, ascending by (pair, assembly, record, start, end, orientation, mm_f, mm_r) -- the order of
+        :func:`seqwin_amd.oligos.amplicons` --, as parallel uint32 arrays of those names and ``n_probe``; ``cell_offsets``
+        (uint64[pairs * assemblies + 1]) bounds the products of every cell.  ValueError on a result made with ``products=False``."""
+        if not self._products:
+            raise ValueError("these amplicons were made with products=False")
+        n_pairs, na, _, _ = self.sizes()
+        n = c_u64()
+        check(lib.sw_amplicons_products_size(self._h, ctypes.byref(n)))
+        offs = np.empty(n_pairs * na + 1, np.uint64)
+        cols = [np.empty(n.value, np.uint32) for _ in PRODUCT_FIELDS]
+        check(lib.sw_amplicons_products(self._h, _ptr(offs), *[_ptr(a) if n.value else None for a in cols]))
+        out = dict(zip(PRODUCT_FIELDS, cols))
+        out["cell_offsets"] = offs
+        return out
+
+    def intervals(self) -> np.ndarray:
+        """INTERVAL_DTYPE ``(record, start, end)`` of every product, in the list's order, as :meth:`Batch.fetch` takes them."""
+        P = self.products()
+        iv = np.empty(len(P["pair"]), INTERVAL_DTYPE)
+        iv["record"], iv["start"], iv["stop"] = P["record"], P["start"], P["end"]
+        return iv
+
+    def stats(self) -> dict:
+        """``items`` (first sites offered to a pair and orientation), ``wave_items`` (those handed to the wave-per-item kernel),
+        ``partners`` (sites visited as the other primer), ``products``, ``detected``, ``launches``; ``count_ms``, ``emit_ms`` and
+        ``order_ms`` (HIP events; the last two are 0 without the list)."""
+        c = (c_u64 * 6)()
+        ms = (ctypes.c_double * 3)()
+        check(lib.sw_amplicons_stats(self._h, c, ms))
+        d = dict(zip(("items", "wave_items", "partners", "products", "detected", "launches"), (int(x) for x in c)))
+        d.update(count_ms=ms[0], emit_ms=ms[1], order_ms=ms[2])
+        return d
+
+    def close(self) -> None:
+        if self._h:
+            lib.sw_amplicons_free(self._h)
             self._h = None
 
     def __del__(self):

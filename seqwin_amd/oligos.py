@@ -67,7 +67,8 @@ def amplicons(hits, lengths, pairs, min_len: int, max_len: int, n_assemblies=Non
     counted; a product may span invalid bases.  Where the sites carry an ``end`` (a search with ``max_edits``: a site with a bulge is
     not L bases long) the product ends at the last site's ``end`` and ``mm_f`` / ``mm_r`` are the sites' ``dist``.  Returns ``(products, n_amplicons)``: a dict of arrays ``pair``, ``assembly``,
     ``record``, ``start``, ``end``, ``orientation``, ``mm_f``, ``mm_r``, ordered by those fields in that order, and
-    ``n_amplicons[n_pairs, n_assemblies]`` (uint32).  ``n_assemblies`` is read from ``hits`` unless given."""
+    ``n_amplicons[n_pairs, n_assemblies]`` (uint32).  ``n_assemblies`` is read from ``hits`` unless given.
+    The same on the device, with probes and a ``dg`` filter: :meth:`seqwin_amd.device.OligoHits.amplicons` (this function is its yardstick)."""
     S = _sites(hits)
     lengths = np.asarray(lengths, np.int64)
     pairs = np.asarray(pairs, np.int64).reshape(-1, 2)
